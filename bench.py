@@ -28,7 +28,17 @@ reported apart and never enters `value`.  The dominant kernel's duration
 comes from HIP events on the stream the kernels run on
 (mp3d_batch_kernel_times).
 
-The CPU baseline (rank 0, N = 1 only) is the oracle restatement built in
+A plain run (`bench.py --gpus N --steps K --warmup W`) sets up, warms up,
+times the K steps and prints the result line, nothing else.  --full adds what
+takes runs of its own: the per-kernel HIP-event times and the roofline
+figures derived from them, the streaming loop (4 segments at N = 1) and the
+CPU baseline; config 1 adds its steady-state latencies and CPU point there.
+--dump-outputs DIR writes what the last timed step left in the caller's
+buffers as DIR/<name>.npy (float32 / float64, a seeded sample of the streams
+where the batch is larger than the sample); the same arguments give the
+same inputs, so two builds can be compared output for output.
+
+The CPU baseline (--full, rank 0, N = 1 only) is the oracle restatement built in
 single precision at -O3 with AVX-512 (oracle/liboracle_f32.so, "port": the
 reference has no decoder to build), timed on a bounded sample of the same
 input on the host threads this process may use, plus single-thread points
@@ -92,6 +102,48 @@ def cpu_model():
         return next(l.split(":", 1)[1].strip() for l in open("/proc/cpuinfo") if l.startswith("model name"))
     except (OSError, StopIteration):
         return ""
+
+
+DUMP_PCM_BYTES = 48e6  # --dump-outputs: float32 PCM of the sampled streams (64 MB bounds all files together)
+DUMP_SEED = 20240607
+
+
+def dump_sample(n, F):
+    """The streams --dump-outputs writes: all of them where their PCM fits
+    DUMP_PCM_BYTES (162 streams of 32 frames), otherwise a fixed, seeded,
+    sorted sample of that many."""
+    m = max(1, int(DUMP_PCM_BYTES // (F * 2304 * 4)))
+    if n <= m:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, m, replace=False)).astype(np.int64)
+
+
+def dump_outputs(dirname, rank, world, arrays):
+    """arrays: name -> numpy array, written as float32 (PCM) or float64 (the
+    rest) to dirname/<name>.npy (<name>_rank<r>.npy with more than one rank)."""
+    d = pathlib.Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32 if name == "pcm" else np.float64)
+        total += a.nbytes
+        np.save(d / (name + ("_rank%d" % rank if world > 1 else "") + ".npy"), a)
+    assert total <= 64e6, total
+    log("rank %d: wrote %s (%.1f MB) to %s" % (rank, ", ".join(arrays), total / 1e6, d))
+
+
+def dump_batch(args, c, last):
+    """The last timed step's PCM (and frame infos, where the path fills
+    them) of the sampled streams, copied out before anything else reuses the
+    buffers."""
+    import torch
+    idx = dump_sample(c.n, c.F)
+    sel = torch.from_numpy(idx).to(c.pcm[0].device)
+    out = {"pcm": c.pcm[last % len(c.pcm)].index_select(0, sel).cpu().numpy()}
+    if getattr(c, "infos", None) is not None:
+        out["infos"] = c.infos.index_select(0, sel).cpu().numpy()
+    out["stream_index"] = idx
+    dump_outputs(args.dump_outputs, c.rank, c.world, out)
 
 
 # ----------------------------------------------------------------------------
@@ -346,8 +398,12 @@ def run_per_frame(args):
     d = mp3_amd.Decoder(device=0)
     data_np = np.frombuffer(data, np.uint8)
     base = data_np.ctypes.data
-    pcm = np.zeros(2304, np.int16)
+    # --dump-outputs: every call of a pass writes its own row (no copy inside
+    # the timed loop), so the rows hold the last pass's PCM afterwards
+    rows = 64 if args.dump_outputs else 1
+    pcm = np.zeros((rows, 2304), np.int16)
     pcm_p = pcm.ctypes.data
+    row_bytes = pcm.strides[0] if rows > 1 else 0
     info = mp3_amd.FrameInfo()
     info_p = ctypes.byref(info)
 
@@ -355,8 +411,9 @@ def run_per_frame(args):
         d.reset()
         pos, nf, lat = 0, 0, []
         while pos < len(data):
+            out_p = pcm_p + min(nf, rows - 1) * row_bytes
             t = time.perf_counter()
-            n = L.mp3d_decode_frame(d._h, base + pos, len(data) - pos, pcm_p, info_p)
+            n = L.mp3d_decode_frame(d._h, base + pos, len(data) - pos, out_p, info_p)
             lat.append(time.perf_counter() - t)
             if n < 0 or info.frame_bytes <= 0:
                 break
@@ -374,6 +431,25 @@ def run_per_frame(args):
         lats += lat
     dt = time.perf_counter() - t0
     lat_us = np.array(lats) * 1e6
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, 0, 1, {"pcm": pcm[:nf]})
+    res = {"metric": METRIC, "value": frames / dt, "unit": "frames/s", "n_gpus": 1, "steps": args.steps,
+           "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
+           "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "tests/golden/keypress_128k_js.mp3",
+           "config": {"workload": "C1: one 128 kbps 44.1 kHz joint-stereo stream (21 audio frames + Info frame) "
+                                  "through mp3d_decode_frame, host buffers, one call per frame",
+                      "streams_per_gpu": 1, "parallelism": "none (per-frame player call)"},
+           "latency_us": {"median": float(np.median(lat_us)), "p90": float(np.percentile(lat_us, 90)),
+                          "p99": float(np.percentile(lat_us, 99)), "mean": float(lat_us.mean())},
+           "readahead_frames": int(os.environ.get("MP3D_PF_READAHEAD", 64)),
+           "note": "one call per frame as a player's loop makes them, the rest of the file passed each time: the "
+                   "decoder reads up to readahead_frames frames ahead in one batch call and serves the next calls "
+                   "from it, while the run after it decodes behind them (MP3D_PF_READAHEAD=0: every call decodes "
+                   "its own frame).  latency_us: every call of the 22-frame file, each pass from reset, so one "
+                   "call in 22 is a cold start; steady_latency_us (--full): a 512-frame stream, its first call apart",
+           "full": args.full, "roofline": None, "cpu_baseline": None}
+    if not args.full:
+        return res
     # steady state of a long stream (the player's case: the read-ahead's
     # next run decodes behind the served calls): a 512-frame 128 kbps golden
     # stream, one call per frame, every call's latency; the first call of a
@@ -431,22 +507,8 @@ def run_per_frame(args):
     cpu = {"value": f1 / (time.perf_counter() - t1), "unit": "frames/s", "cores": 1, "kind": "port",
            "sample": "the same file decoded repeatedly for 2 s by oracle/liboracle_f32.so on one thread",
            "cpu_model": cpu_model()}
-    return {"metric": METRIC, "value": frames / dt, "unit": "frames/s", "n_gpus": 1, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "tests/golden/keypress_128k_js.mp3",
-            "config": {"workload": "C1: one 128 kbps 44.1 kHz joint-stereo stream (21 audio frames + Info frame) "
-                                   "through mp3d_decode_frame, host buffers, one call per frame",
-                       "streams_per_gpu": 1, "parallelism": "none (per-frame player call)"},
-            "latency_us": {"median": float(np.median(lat_us)), "p90": float(np.percentile(lat_us, 90)),
-                           "p99": float(np.percentile(lat_us, 99)), "mean": float(lat_us.mean())},
-            "steady_latency_us": steady,
-            "readahead_frames": int(os.environ.get("MP3D_PF_READAHEAD", 64)),
-            "note": "one call per frame as a player's loop makes them, the rest of the file passed each time: the "
-                    "decoder reads up to readahead_frames frames ahead in one batch call and serves the next calls "
-                    "from it, while the run after it decodes behind them (MP3D_PF_READAHEAD=0: every call decodes "
-                    "its own frame).  latency_us: every call of the 22-frame file, each pass from reset, so one "
-                    "call in 22 is a cold start; steady_latency_us: a 512-frame stream, its first call apart",
-            "roofline": None, "cpu_baseline": cpu}
+    res.update(steady_latency_us=steady, cpu_baseline=cpu)
+    return res
 
 
 def main():
@@ -460,7 +522,13 @@ def main():
     ap.add_argument("--frames", type=int, default=None, help="frames per stream per step (default: the config's)")
     ap.add_argument("--seed", type=int, default=None,
                     help="generator seed of global stream 0 (stream g uses seed + g; default: the config's)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: per-kernel times and roofline, the "
+                         "streaming loop, the CPU baseline (config 1: steady-state latencies and its CPU point)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the last step's outputs (PCM, frame infos; a seeded sample of "
+                         "the streams of a large batch) to DIR/<name>.npy as float32 / float64")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--gather", action="store_true",
                     help="also time an RCCL PCM gather to rank 0 overlapped with the next step (reported apart)")
     ap.add_argument("--gather-priority", default="normal", choices=("high", "normal"),
@@ -471,11 +539,14 @@ def main():
                          "multi-rank path, e.g. several ranks on one GPU)")
     ap.add_argument("--streaming", type=int, default=None, metavar="SEGMENTS",
                     help="also time the streaming loop: streams of SEGMENTS x frames, each step decoding the next "
-                         "frames (new offsets every call); reported as `streaming` (default 4 at N = 1, 0 = off)")
+                         "frames (new offsets every call); reported as `streaming` (default: 4 with --full at "
+                         "N = 1, otherwise 0 = off)")
     ap.add_argument("--plumbing", action="store_true",
                     help="no GPU: exercise the launcher, rendezvous, sharding, barriers, max-over-ranks timing and "
                          "the gather on CPU tensors (gloo); value is null (tests/test_bench_launch.py)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))
@@ -600,15 +671,17 @@ def main():
     frames_total = sum(per_rank_frames) * args.steps
     value = frames_total / dt
     ms_per_step = dt / args.steps * 1e3
+    if args.dump_outputs:
+        dump_batch(args, c, args.steps - 1)
 
-    # --- per-kernel device time (HIP events on the decode stream) ---------
-    kt = {"demux": 0.0, "huffman": 0.0, "synth": 0.0}
-    if not args.plumbing:
+    # --- per-kernel device time (HIP events on the decode stream; --full) -
+    kt = None
+    if args.full and not args.plumbing:
         c.dec.set_timing(True)
         # the median of the timed calls: C2's calls are ~0.3 ms, and single
         # ones ran up to 35 % long (clock ramp after the host-side gaps)
         reps = max(1, min(9 if cfg == "c2" else 3, args.steps))
-        samples = {key: [] for key in kt}
+        samples = {"demux": [], "huffman": [], "synth": []}
         for k in range(reps):
             c.step(k)
             for key, v in c.dec.kernel_times_us().items():
@@ -620,7 +693,7 @@ def main():
 
     # --- streaming loop: new stream geometry on every call ----------------
     streaming = None
-    segs = args.streaming if args.streaming is not None else (4 if world == 1 else 0)
+    segs = args.streaming if args.streaming is not None else (4 if args.full and world == 1 else 0)
     if segs > 0 and cfg != "c2" and not args.plumbing:
         sstep = setup_streaming(c, segs)
         for k in range(args.warmup):
@@ -663,7 +736,7 @@ def main():
         return
     res = {"metric": METRIC, "value": None if args.plumbing else value, "unit": "frames/s", "n_gpus": world,
            "ranks": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
-           "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
+           "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "full": args.full,
            "per_rank_frames_per_s": [f * args.steps / t for f, t in zip(per_rank_frames, per_rank_dt)],
            "dist_backend": backend if use_group else None,
            "setup_s_per_rank": setup_all, "gen_threads_per_rank": c.gen_threads}
@@ -777,10 +850,6 @@ def load_pmc(key, n, F):
 
 def report_decode(c, args, cfg, value, kt, frames_per_step):
     n, F, world = c.n, c.F, c.world
-    synth_s = kt["synth"] * 1e-6
-    frames_per_launch = n * F
-    achieved_tf = FLOP_PER_FRAME * frames_per_launch / synth_s / 1e12 if synth_s > 0 else 0.0
-    pmc = load_pmc(cfg, n, F)
     in_per_frame = c.in_bytes / max(1, frames_per_step)
     if cfg == "c3":
         if world == 8 and n == 65536:
@@ -792,16 +861,26 @@ def report_decode(c, args, cfg, value, kt, frames_per_step):
         wl = "C5: mixed corpus (VBR 32-320 kbps, mono/stereo/MS/IS, 32/44.1/48 kHz, short+mixed blocks, CRC), " \
              "%d streams x %d frames per GPU per step" % (n, F)
         data = "synthetic (seeded generator: mixed-corpus MP3 streams)"
+    config = {"workload": wl, "streams_per_gpu": n, "frames_per_stream": F, "bitrate_kbps": 128 if cfg == "c3"
+              else "32-320 VBR", "hz": 44100 if cfg == "c3" else "32000/44100/48000",
+              "seed": c.seed if c.seed is not None else "default",
+              "parallelism": "streams sharded, 1 process per GPU, no data-path collective"}
+    hbm = {"hbm_rw_frac": value / world * (in_per_frame + PCM_BYTES_PER_FRAME) / (HBM_PEAK_GBS * 1e9),
+           "hbm_read_frac": value / world * in_per_frame / (HBM_PEAK_GBS * 1e9),
+           "bytes_per_frame_rw": in_per_frame + PCM_BYTES_PER_FRAME}
+    if kt is None:  # a plain run: no per-kernel times, hence no roofline, and no CPU baseline (--full)
+        return {"data": data, "config": config, "roofline": None, "hbm": hbm, "cpu_baseline": None}
+    synth_s = kt["synth"] * 1e-6
+    frames_per_launch = n * F
+    achieved_tf = FLOP_PER_FRAME * frames_per_launch / synth_s / 1e12 if synth_s > 0 else 0.0
+    pmc = load_pmc(cfg, n, F)
     cpu = None
     if not args.no_cpu_baseline and world == 1:
         cpu = cpu_baseline_decode(c.buf, c.offs, c.sizes, F)
     dom = max(kt, key=kt.get)
     return {
         "data": data,
-        "config": {"workload": wl, "streams_per_gpu": n, "frames_per_stream": F, "bitrate_kbps": 128 if cfg == "c3"
-                   else "32-320 VBR", "hz": 44100 if cfg == "c3" else "32000/44100/48000",
-                   "seed": c.seed if c.seed is not None else "default",
-                   "parallelism": "streams sharded, 1 process per GPU, no data-path collective"},
+        "config": config,
         "roofline": {
             "kernel": "k_synth", "bound": "mfma", "roofline_class": "FP32 compute", "unit": "TFLOP/s",
             "bound_detail": "compute roofline at the dense FP32 peak (MFMA rate = vector rate); the kernel's limiter is "
@@ -828,12 +907,7 @@ def report_decode(c, args, cfg, value, kt, frames_per_step):
                 "note": "matrix-core busy fraction of k_synth from rocprofv3 (SQ_VALU_MFMA_BUSY_CYCLES, "
                         "profiles/pmc_traffic.json); peak 157.3 TFLOP/s FP32 MFMA"},
         },
-        "hbm": {
-            "hbm_rw_frac": value / world * (in_per_frame + PCM_BYTES_PER_FRAME) / (HBM_PEAK_GBS * 1e9),
-            "hbm_read_frac": value / world * in_per_frame / (HBM_PEAK_GBS * 1e9),
-            "bytes_per_frame_rw": in_per_frame + PCM_BYTES_PER_FRAME,
-            "step_traffic_pmc": pmc.get("step_hbm_bytes"),
-        },
+        "hbm": dict(hbm, step_traffic_pmc=pmc.get("step_hbm_bytes")),
         "kernel_us": kt,
         "kernel_us_stat": "median over %d HIP-event-timed calls after the timed loop" % getattr(c, "kt_reps", 0),
         "dominant_kernel": "k_" + dom,
@@ -843,6 +917,15 @@ def report_decode(c, args, cfg, value, kt, frames_per_step):
 
 def report_c2(c, args, value, kt):
     n, F, world = c.n, c.F, c.world
+    data = "synthetic spectra (SURVEY.md §8(d) C2: N(0, sigma_k^2) with spectral tilt, start/short/stop runs, " \
+           "mixed blocks)"
+    config = {"workload": "C2: IMDCT + polyphase synthesis only (mp3d_batch_synth_only), %d streams x %d "
+                          "frames per GPU per step" % (n, F),
+              "streams_per_gpu": n, "frames_per_stream": F, "hz": 44100,
+              "seed": c.seed if c.seed is not None else "default",
+              "parallelism": "streams sharded, 1 process per GPU, no data-path collective"}
+    if kt is None:  # a plain run (see report_decode)
+        return {"data": data, "config": config, "roofline": None, "cpu_baseline": None}
     synth_s = kt["synth"] * 1e-6
     fpl = n * F
     achieved_tf = C2_FLOP_PER_FRAME * fpl / synth_s / 1e12 if synth_s > 0 else 0.0
@@ -852,13 +935,8 @@ def report_c2(c, args, value, kt):
     if not args.no_cpu_baseline and world == 1:
         cpu = cpu_baseline_synth(c.xr, c.bt, c.mx, 2)
     return {
-        "data": "synthetic spectra (SURVEY.md §8(d) C2: N(0, sigma_k^2) with spectral tilt, start/short/stop runs, "
-                "mixed blocks)",
-        "config": {"workload": "C2: IMDCT + polyphase synthesis only (mp3d_batch_synth_only), %d streams x %d "
-                               "frames per GPU per step" % (n, F),
-                   "streams_per_gpu": n, "frames_per_stream": F, "hz": 44100,
-                   "seed": c.seed if c.seed is not None else "default",
-                   "parallelism": "streams sharded, 1 process per GPU, no data-path collective"},
+        "data": data,
+        "config": config,
         "roofline": {
             "kernel": "k_synth<xr>", "bound": "mfma", "roofline_class": "FP32 compute",
             "bound_detail": "compute roofline at the dense FP32 peak (MFMA rate = vector rate); VALU-issue limited",

@@ -42,6 +42,21 @@ def test_bench_single_rank_no_spawn():
     assert r["n_gpus"] == 1 and r["ranks"] == 1 and r["dist_backend"] is None
 
 
+def test_bench_full_and_dump_outputs(tmp_path):
+    """--full is accepted and reported; --dump-outputs writes the last step's
+    buffers as float32 / float64 .npy files within 64 MB."""
+    import numpy as np
+    r = _run("--gpus", "1", "--full", "--dump-outputs", str(tmp_path / "out"))
+    assert r["full"] is True and r["steps"] == 2 and r["ms_per_step"] >= 0
+    n, F = r["config"]["streams_per_gpu"], r["config"]["frames_per_stream"]
+    files = sorted(p.name for p in (tmp_path / "out").iterdir())
+    assert files == ["pcm.npy", "stream_index.npy"], files
+    pcm = np.load(tmp_path / "out" / "pcm.npy")
+    idx = np.load(tmp_path / "out" / "stream_index.npy")
+    assert pcm.dtype == np.float32 and pcm.shape == (n, F, 2304) and idx.dtype == np.float64
+    assert np.array_equal(idx, np.arange(n)) and pcm.nbytes + idx.nbytes <= 64e6
+
+
 def test_bench_rank_failure_propagates():
     env = {k: v for k, v in os.environ.items() if k != "WORLD_SIZE"}
     env["WORLD_SIZE"] = "3"  # torchrun-style single rank whose world disagrees with --gpus
