@@ -227,6 +227,75 @@ MP3D_API int mp3d_batch_set_state(mp3d_batch *b, int first, int n, const void *b
 MP3D_API int mp3d_dec_get_state(mp3d_dec *dec, void *buf);
 MP3D_API int mp3d_dec_set_state(mp3d_dec *dec, const void *buf);
 
+/* ---- packed uniform-rate PCM sink --------------------------------------- *
+ * Instead of [n][F][2304] rows at each stream's own rate and channel count,
+ * a packed call writes every stream's samples contiguously at ONE rate and
+ * channel count, resampled and down/up-mixed on the GPU.  The resampler keeps
+ * per-stream state in the handle (not in the state blob), so a stream decoded
+ * in calls of any size gives the same samples as one call.
+ *
+ * Filter (for in_hz, out_hz from 8000, 11025, 12000, 16000, 22050, 24000,
+ * 32000, 44100, 48000):
+ *   g = gcd(in_hz, out_hz); L = out_hz / g; M = in_hz / g
+ *   r = min(1, L / M); W = 24 / r; T = 2 ceil(W)        taps per phase
+ *   t = p / L - (j - (T/2 - 1))
+ *   w = I0(9 sqrt(1 - (t/W)^2)) / I0(9) for |t| < W, else 0   (Kaiser, beta 9)
+ *   h = 0.88 r sinc(0.88 r t) w;   taps[p][j] = h / sum_j h
+ *   y[m] = sum_j taps[p][j] x[n0 - (T/2 - 1) + j], n0 = floor(m M / L),
+ *   p = (m M) mod L, x[n < 0] = 0: y[m] sits at time m / out_hz, no delay.
+ * The products are accumulated in float32 in ascending j.  in_hz == out_hz
+ * is a bypass (L = M = T = 1): the samples are copied.  Before the filter
+ * the channels are mapped: mono -> stereo duplicates, stereo -> mono is
+ * 0.5f * (l + r); a stream may switch between mono and stereo frames.
+ *
+ * A stream's input rate is fixed by its first audio frame after a restart;
+ * later frames that report another hz are fed at that rate (their infos keep
+ * their own hz).  An output is emitted once every input it needs has been
+ * seen (n0 + T/2 <= inputs seen - 1); the tail waits for the next call.  A
+ * stream's resampler restarts (history zero, m = 0) at create, at
+ * mp3d_batch_reset, at mp3d_batch_set_state on its slot, at a change of the
+ * output format, and after its own flush.                                   */
+
+/* host only, no GPU: taps[L][T] floats (NULL: sizes only); cap = floats taps
+ * can hold; returns L * T or MP3D_E_ARG */
+MP3D_API long long mp3d_resample_filter(int in_hz, int out_hz, int *L, int *M, int *T, float *taps, size_t cap);
+
+/* out_hz from the nine rates, out_channels 1 or 2; out_hz = 0 turns the sink
+ * off and frees its buffers.  Waits for the handle's work. */
+MP3D_API int mp3d_batch_set_output(mp3d_batch *b, int out_hz, int out_channels);
+
+/* smallest out_stride that can never overflow: the most samples per channel
+ * one call of `frames` frames per stream can emit for any input rate
+ * >= min_in_hz (the pending tail of earlier calls included); 0 when
+ * min_in_hz is above 48000 */
+MP3D_API long long mp3d_packed_max_samples(int out_hz, int frames, int min_in_hz);
+
+/* Decodes like mp3d_batch_decode_f32 (the decoder state advances exactly so),
+ * then stream s writes out_count[s] samples per channel, interleaved, at
+ * out + s * out_stride * out_channels elements; nothing past them is touched.
+ * out is float32 when f32 != 0, else int16 (clamp(floor(y * 32768 + 0.5))).
+ * out, out_count and infos (may be NULL) are host or device memory; the call
+ * is asynchronous when all of them are device memory.  MP3D_PACK_FLUSH feeds
+ * zeros after the call's frames, so a stream's lifetime total is exactly
+ * ceil(N L / M) for its N input samples, and its resampler restarts.  A
+ * stream that would exceed out_stride gets out_count[s] = -1, writes nothing
+ * and has its resampler restarted.  MP3D_E_ARG before mp3d_batch_set_output.
+ * A device out must be aligned to one sample frame (out_channels elements: 8
+ * bytes for float32 stereo, 4 for int16 stereo or float32 mono), else
+ * MP3D_E_ARG; a host out may sit anywhere.  A host (or other-GPU) out is
+ * filled from a staging buffer by one copy of out_count[s] samples per
+ * stream, which keeps the bytes past them untouched but costs n_streams
+ * copies per call: meant for small batches, wide ones pass device memory.   */
+#define MP3D_PACK_FLUSH 1
+MP3D_API int mp3d_batch_decode_packed(mp3d_batch *b, const uint8_t *frames, const uint64_t *offsets,
+                                      const uint32_t *sizes, int n_streams, int frames_per_stream, void *out, int f32,
+                                      long long out_stride, int *out_count, int flags, mp3d_frame_info *infos,
+                                      void *hip_stream);
+
+/* device-side microseconds of the resample stage of the last packed call
+ * (needs mp3d_batch_set_timing) */
+MP3D_API int mp3d_batch_resample_time(mp3d_batch *b, float *us);
+
 /* ---- diagnostics -------------------------------------------------------- */
 MP3D_API const char *mp3d_strerror(int err);
 MP3D_API int mp3d_last_hip_error(void);

@@ -49,9 +49,12 @@ EXPORTS = ["mp3d_dec_create", "mp3d_dec_create_on", "mp3d_dec_destroy", "mp3d_de
            "mp3d_dec_stream_info", "mp3d_batch_decode_long",
            "mp3d_long_plan", "mp3d_batch_set_options", "mp3d_dec_set_options", "mp3d_decode_frame_ex",
            "mp3d_state_bytes", "mp3d_batch_get_state", "mp3d_batch_set_state", "mp3d_dec_get_state",
-           "mp3d_dec_set_state"]
+           "mp3d_dec_set_state", "mp3d_resample_filter", "mp3d_batch_set_output", "mp3d_packed_max_samples",
+           "mp3d_batch_decode_packed", "mp3d_batch_resample_time"]
 
 OPT_CRC_CHECK = 1  # MP3D_OPT_CRC_CHECK: drop frames whose CRC-16 mismatches
+PACK_FLUSH = 1  # MP3D_PACK_FLUSH: feed zeros after the call's frames, then restart the resamplers
+RATES = (8000, 11025, 12000, 16000, 22050, 24000, 32000, 44100, 48000)
 FRAME_F32, FRAME_LAST = 1, 2  # mp3d_decode_frame_ex flags
 
 _lib = None
@@ -104,6 +107,14 @@ def lib():
         L.mp3d_batch_set_state.argtypes = [vp, i, i, vp]
         L.mp3d_dec_get_state.argtypes = [vp, vp]
         L.mp3d_dec_set_state.argtypes = [vp, vp]
+        ip = ctypes.POINTER(ctypes.c_int)
+        L.mp3d_resample_filter.argtypes = [i, i, ip, ip, ip, vp, ctypes.c_size_t]
+        L.mp3d_resample_filter.restype = ctypes.c_longlong
+        L.mp3d_batch_set_output.argtypes = [vp, i, i]
+        L.mp3d_packed_max_samples.argtypes = [i, i, i]
+        L.mp3d_packed_max_samples.restype = ctypes.c_longlong
+        L.mp3d_batch_decode_packed.argtypes = [vp, vp, u64p, u32p, i, i, vp, i, ctypes.c_longlong, vp, i, vp, vp]
+        L.mp3d_batch_resample_time.argtypes = [vp, vp]
         _lib = L
     return _lib
 
@@ -274,6 +285,51 @@ class BatchDecoder:
         _check(fn(self._h, fp, off.ctypes.data, sz.ctypes.data, n, F, pp, ip, ctypes.c_void_p(stream) if stream else None))
         return pcm, infos
 
+    def set_output(self, hz, channels):
+        """Format of the packed sink (decode_packed): hz from RATES, channels
+        1 or 2; hz = 0 turns the sink off and frees its buffers.  A change
+        restarts every stream's resampler."""
+        _check(lib().mp3d_batch_set_output(self._h, int(hz), int(channels)))
+        self._out = (int(hz), int(channels))
+
+    def decode_packed(self, frames, offsets, sizes, frames_per_stream, out=None, counts=None, infos=None, f32=True,
+                      flush=False, stride=None, stream=None):
+        """Decode and write every stream's samples contiguously at the rate
+        and channel count of set_output (mp3d_batch_decode_packed).  out: None
+        (allocate host) or float32 (int16 with f32=False) array/tensor
+        [n, stride, channels]; counts: None or int32 array/tensor [n]; infos as
+        in decode.  stride defaults to out's, else to the bound that cannot
+        overflow.  flush=True ends the streams: the filter tails are emitted
+        and the resamplers restart.  Returns (out, counts, infos); stream s
+        holds counts[s] samples per channel (-1: over the stride)."""
+        off, sz = self._geom(offsets, sizes)
+        n, F = off.size, int(frames_per_stream)
+        hz, ch = getattr(self, "_out", (0, 0))
+        if stride is None:  # (no format set: the call below fails with MP3D_E_ARG)
+            stride = int(out.shape[1]) if out is not None else packed_max_samples(hz, F) if hz else 1
+        stride = int(stride)
+        if out is None:
+            out = np.zeros((n, stride, ch), np.float32 if f32 else np.int16)
+        if counts is None:
+            counts = np.zeros(n, np.int32)
+        if infos is None:
+            infos = np.zeros((n, F), FRAME_INFO_DT)
+        fp, k1 = _ptr(frames)
+        op, k2 = _ptr(out)
+        cp, k3 = _ptr(counts)
+        ip, k4 = _ptr(infos)
+        _check(lib().mp3d_batch_decode_packed(self._h, fp, off.ctypes.data, sz.ctypes.data, n, F, op, int(bool(f32)),
+                                              stride, cp, PACK_FLUSH if flush else 0, ip,
+                                              ctypes.c_void_p(stream) if stream else None))
+        return out, counts, infos
+
+    def resample_time_us(self):
+        """Device-side microseconds of the resample stage of the last packed
+        call (after set_timing)."""
+        t = ctypes.c_float()
+        _check(lib().mp3d_batch_resample_time(self._h, ctypes.byref(t)))
+        return float(t.value)
+
     @staticmethod
     def _nbytes(x):
         """Byte size of a contiguous host array / device tensor (its element
@@ -384,6 +440,23 @@ class BatchDecoder:
 def state_bytes():
     """Bytes of one stream's opaque decoder state (mp3d_state_bytes)."""
     return int(lib().mp3d_state_bytes())
+
+
+def resample_filter(in_hz, out_hz):
+    """The packed sink's polyphase filter (mp3d_resample_filter; no GPU
+    needed): (L, M, taps float32 [L, T])."""
+    L, M, T = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    n = _check(lib().mp3d_resample_filter(int(in_hz), int(out_hz), ctypes.byref(L), ctypes.byref(M), ctypes.byref(T),
+                                          None, 0))
+    taps = np.zeros(n, np.float32)
+    _check(lib().mp3d_resample_filter(int(in_hz), int(out_hz), None, None, None, taps.ctypes.data, taps.size))
+    return L.value, M.value, taps.reshape(L.value, T.value)
+
+
+def packed_max_samples(out_hz, frames, min_in_hz=8000):
+    """Smallest stride of decode_packed that can never overflow for streams
+    of input rate >= min_in_hz (mp3d_packed_max_samples)."""
+    return int(_check(lib().mp3d_packed_max_samples(int(out_hz), int(frames), int(min_in_hz))))
 
 
 def max_frame_slots(nbytes):

@@ -26,6 +26,7 @@
 #include "mp3d_tables.h"
 #include "mp3d_consts.h"
 #include "mp3d_hostparse.h"
+#include "mp3d_resample.h"
 
 namespace mp3d {
 hipError_t upload_synth_constants(const float *, const float *, const float *, const float *);
@@ -47,6 +48,8 @@ void launch_lds_poison(int, hipStream_t);
 void launch_frame(const uint8_t *, uint32_t, const uint64_t *, const uint32_t *, uint8_t *, const uint64_t *,
                   StreamState *, FrameRec *, uint64_t *, void *, int, const DevTables *, int16_t *, UnitMeta *, void *,
                   bool, bool, uint32_t *, uint32_t, hipStream_t);
+void launch_resample(const float *, const void *, RsState *, const RsCfg *, int, const float *, RsPlan *, int32_t *,
+                     void *, bool, int32_t *, int, int, long long, int, int, hipStream_t);
 } // namespace mp3d
 
 using namespace mp3d;
@@ -386,6 +389,24 @@ struct mp3d_batch {
     hipStream_t last_s = nullptr; /* compared with the next call's, never used */
     hipEvent_t ev[4] = {};
     bool poison = false; /* MP3D_DEBUG_POISON at create */
+    /* packed PCM sink (mp3d_batch_set_output; mp3d_resample.h): rs_hz = 0 is
+     * off, and then none of these buffers exists.  rs_st, rs_plan, rs_cnt
+     * hold max_streams entries; rs_rows (the float32 rows of a packed call),
+     * rs_prefix and rs_out (staging for a host sink) grow with the calls. */
+    int rs_hz = 0, rs_ch = 0;
+    RsCfg rs_cfg = {};
+    RsCfg *rs_dcfg = nullptr;
+    RsState *rs_st = nullptr;
+    RsPlan *rs_plan = nullptr;
+    int32_t *rs_cnt = nullptr;
+    float *rs_tab = nullptr;
+    size_t rs_dcfg_cap = 0, rs_st_cap = 0, rs_plan_cap = 0, rs_cnt_cap = 0, rs_tab_cap = 0;
+    float *rs_rows = nullptr;
+    int32_t *rs_prefix = nullptr;
+    void *rs_out = nullptr;
+    size_t rs_rows_cap = 0, rs_prefix_cap = 0, rs_out_cap = 0;
+    hipEvent_t ev_rs[2] = {};
+    bool rs_timed = false; /* ev_rs hold a packed call's stage */
 };
 
 /* an event after all of the handle's work issued so far */
@@ -593,6 +614,7 @@ extern "C" int mp3d_batch_create(int device, int max_streams, int max_frames, mp
         return MP3D_E_HIP;
     }
     for (int i = 0; i < 4; i++) (void)hipEventCreate(&b->ev[i]);
+    for (int i = 0; i < 2; i++) (void)hipEventCreate(&b->ev_rs[i]);
     b->poison = poison_env();
     if (b->poison) {
         const size_t fr = (size_t)max_streams * max_frames;
@@ -632,7 +654,8 @@ extern "C" void mp3d_batch_destroy(mp3d_batch *b) {
     if (b->own) (void)hipStreamSynchronize(b->own);
     if (b->copy) (void)hipStreamSynchronize(b->copy);
     void *ptrs[] = {b->st, b->rec, b->sideu, b->is_buf, b->meta, b->rank, b->geo[0].d, b->geo[1].d, b->d_work,
-                    b->d_infos, b->md, b->d_in, b->d_pcm, b->d_xr, b->d_bt, b->d_mx, b->st_tail[0], b->st_tail[1]};
+                    b->d_infos, b->md, b->d_in, b->d_pcm, b->d_xr, b->d_bt, b->d_mx, b->st_tail[0], b->st_tail[1],
+                    b->rs_dcfg, b->rs_st, b->rs_plan, b->rs_cnt, b->rs_tab, b->rs_rows, b->rs_prefix, b->rs_out};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     for (auto &g : b->geo) {
@@ -641,6 +664,8 @@ extern "C" void mp3d_batch_destroy(mp3d_batch *b) {
         if (g.freed) (void)hipEventDestroy(g.freed);
     }
     for (hipEvent_t e : b->ev)
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : b->ev_rs)
         if (e) (void)hipEventDestroy(e);
     if (b->ev_done) (void)hipEventDestroy(b->ev_done);
     if (b->own) (void)hipStreamDestroy(b->own);
@@ -655,6 +680,7 @@ extern "C" int mp3d_batch_reset(mp3d_batch *b) {
     if (r) return r;
     b->tail_live = -1; /* the state is zeroed whole */
     HIPCHK(state_clear(b->st, b->max_streams, b->own));
+    if (b->rs_st) HIPCHK(hipMemsetAsync(b->rs_st, 0, sizeof(RsState) * (size_t)b->max_streams, b->own));
     HIPCHK(hipStreamSynchronize(b->own));
     return MP3D_OK;
 }
@@ -1912,6 +1938,8 @@ static int state_copy(mp3d_batch *b, int first, int n, void *dst, const void *sr
     StreamState *at = b->st + first;
     HIPCHK(hipMemcpyAsync(out ? dst : (void *)at, out ? (const void *)at : src, sizeof(StreamState) * (size_t)n,
                           hipMemcpyDefault, s));
+    /* a restored state is a discontinuity: the slots' resamplers restart */
+    if (!out && b->rs_st) HIPCHK(hipMemsetAsync(b->rs_st + first, 0, sizeof(RsState) * (size_t)n, s));
     HIPCHK(hipStreamSynchronize(s));
     return MP3D_OK;
 }
@@ -1949,6 +1977,248 @@ extern "C" int mp3d_dec_set_state(mp3d_dec *d, const void *buf) {
     HIPCHK(hipMemcpy(&h, d->b->st, sizeof(h), hipMemcpyDeviceToHost));
     d->kind = h.kind;
     d->frames = (long)h.frames + (h.tag_info ? 1 : 0);
+    return MP3D_OK;
+}
+
+/* ------------------------------------------------------------------------ */
+/* Packed uniform-rate PCM sink (DESIGN.md "Packed PCM sink")                */
+/* ------------------------------------------------------------------------ */
+static const int RS_RATES[MP3D_RS_RATES] = {8000, 11025, 12000, 16000, 22050, 24000, 32000, 44100, 48000};
+static int rs_rate_index(int hz) {
+    for (int i = 0; i < MP3D_RS_RATES; i++)
+        if (RS_RATES[i] == hz) return i;
+    return -1;
+}
+static long long rs_gcd(long long a, long long b) {
+    while (b) {
+        const long long t = a % b;
+        a = b;
+        b = t;
+    }
+    return a;
+}
+/* modified Bessel function I0 by its power series (x <= 9 here) */
+static double rs_i0(double x) {
+    double sum = 1.0, term = 1.0;
+    const double q = x * x / 4.0;
+    for (int k = 1; k < 200; k++) {
+        term *= q / ((double)k * k);
+        sum += term;
+        if (term < 1e-20 * sum) break;
+    }
+    return sum;
+}
+static void rs_sizes(int in_hz, int out_hz, int *L, int *M, int *T) {
+    if (in_hz == out_hz) {
+        *L = *M = *T = 1;
+        return;
+    }
+    const int g = (int)rs_gcd(in_hz, out_hz);
+    *L = out_hz / g;
+    *M = in_hz / g;
+    /* W = 24 / r = 24 M / L when downsampling, else 24; T = 2 ceil(W) */
+    *T = *L < *M ? 2 * (int)((24LL * *M + *L - 1) / *L) : 48;
+}
+/* the Kaiser-windowed sinc of include/mp3d.h, taps[L][T] (row stride ld) */
+static void rs_design(int L, int M, int T, float *taps, int ld) {
+    if (T == 1) {
+        taps[0] = 1.0f;
+        return;
+    }
+    const double r = L < M ? (double)L / M : 1.0, W = 24.0 / r, i0b = rs_i0(9.0);
+    std::vector<double> h((size_t)T);
+    for (int p = 0; p < L; p++) {
+        double sum = 0.0;
+        for (int j = 0; j < T; j++) {
+            const double t = (double)p / L - (j - (T / 2 - 1));
+            double w = 0.0;
+            if (fabs(t) < W) w = rs_i0(9.0 * sqrt(1.0 - (t / W) * (t / W))) / i0b;
+            const double x = 0.88 * r * t;
+            const double sinc = x == 0.0 ? 1.0 : sin(M_PI * x) / (M_PI * x);
+            h[j] = 0.88 * r * sinc * w;
+            sum += h[j];
+        }
+        for (int j = 0; j < T; j++) taps[(size_t)p * ld + j] = (float)(h[j] / sum);
+    }
+}
+
+extern "C" long long mp3d_resample_filter(int in_hz, int out_hz, int *L, int *M, int *T, float *taps, size_t cap) {
+    if (rs_rate_index(in_hz) < 0 || rs_rate_index(out_hz) < 0) return MP3D_E_ARG;
+    int l, m, t;
+    rs_sizes(in_hz, out_hz, &l, &m, &t);
+    if (L) *L = l;
+    if (M) *M = m;
+    if (T) *T = t;
+    const long long n = (long long)l * t;
+    if (taps) {
+        if ((long long)cap < n) return MP3D_E_ARG;
+        rs_design(l, m, t, taps, t);
+    }
+    return n;
+}
+
+/* the most outputs one call of `frames` frames at in_hz can emit: all its
+ * inputs plus a pending tail of `post` inputs, ceil((N + post) L / M) */
+static long long rs_bound(int in_hz, int out_hz, long long frames) {
+    int L, M, T;
+    rs_sizes(in_hz, out_hz, &L, &M, &T);
+    const long long N = frames * (in_hz >= 32000 ? 1152 : 576) + (T == 1 ? 0 : T / 2);
+    return (N * L + M - 1) / M;
+}
+
+extern "C" long long mp3d_packed_max_samples(int out_hz, int frames, int min_in_hz) {
+    if (rs_rate_index(out_hz) < 0 || frames < 0) return MP3D_E_ARG;
+    long long best = 0;
+    for (int hz : RS_RATES)
+        if (hz >= min_in_hz) best = std::max(best, rs_bound(hz, out_hz, frames));
+    return best;
+}
+
+static void rs_free(mp3d_batch *b) {
+    void **ptrs[] = {(void **)&b->rs_dcfg, (void **)&b->rs_st,   (void **)&b->rs_plan,   (void **)&b->rs_cnt,
+                     (void **)&b->rs_tab,  (void **)&b->rs_rows, (void **)&b->rs_prefix, &b->rs_out};
+    for (void **p : ptrs) {
+        if (*p) (void)hipFree(*p);
+        *p = nullptr;
+    }
+    b->rs_dcfg_cap = b->rs_st_cap = b->rs_plan_cap = b->rs_cnt_cap = b->rs_tab_cap = 0;
+    b->rs_rows_cap = b->rs_prefix_cap = b->rs_out_cap = 0;
+    b->rs_hz = b->rs_ch = 0;
+    b->rs_timed = false;
+}
+
+extern "C" int mp3d_batch_set_output(mp3d_batch *b, int out_hz, int out_channels) {
+    if (!b) return MP3D_E_ARG;
+    if (out_hz != 0 && (rs_rate_index(out_hz) < 0 || (out_channels != 1 && out_channels != 2))) return MP3D_E_ARG;
+    HIPCHK(hipSetDevice(b->device));
+    int r = own_after_last(b);
+    if (r) return r;
+    HIPCHK(hipStreamSynchronize(b->own));
+    if (out_hz == 0) {
+        rs_free(b);
+        return MP3D_OK;
+    }
+    /* one filter per input rate; rows padded to 4 floats for 16-byte loads */
+    RsCfg cfg = {};
+    cfg.out_ch = out_channels;
+    std::vector<float> tab;
+    for (int i = 0; i < MP3D_RS_RATES; i++) {
+        RsFilt &f = cfg.f[i];
+        rs_sizes(RS_RATES[i], out_hz, &f.L, &f.M, &f.T);
+        f.Tp = (f.T + 3) & ~3;
+        f.pre = f.T == 1 ? 0 : f.T / 2 - 1;
+        f.post = f.T == 1 ? 0 : f.T / 2;
+        f.off = (int32_t)tab.size();
+        tab.resize(tab.size() + (size_t)f.L * f.Tp, 0.0f);
+        rs_design(f.L, f.M, f.T, tab.data() + f.off, f.Tp);
+        /* a tile's input span is at most (tile - 1) M / L + 1 + T samples */
+        long long tile = std::max<long long>(1, (long long)(MP3D_RS_SPAN - f.T - 2) * f.L / f.M);
+        f.S = MP3D_RS_THREADS;
+        if (f.T == MP3D_RS_UP_TAPS) {
+            /* a thread's output stride: the multiple of L (<= 2048, or L) that
+             * fills whole passes of the block best */
+            double best = -1.0;
+            for (int c = 1; c == 1 || c * f.L <= 2048; c++) {
+                const int S = c * f.L, passes = (S + MP3D_RS_THREADS - 1) / MP3D_RS_THREADS;
+                const double fill = (double)S / (passes * MP3D_RS_THREADS);
+                if (fill > best + 1e-9) {
+                    best = fill;
+                    f.S = S;
+                }
+            }
+            tile = std::min<long long>(tile, std::max(4096, 8 * f.S));
+        }
+        f.tile = (int32_t)tile;
+    }
+    const size_t ns = (size_t)b->max_streams;
+    r = grow(b, (void **)&b->rs_dcfg, &b->rs_dcfg_cap, sizeof(RsCfg));
+    if (!r) r = grow(b, (void **)&b->rs_st, &b->rs_st_cap, sizeof(RsState) * ns);
+    if (!r) r = grow(b, (void **)&b->rs_plan, &b->rs_plan_cap, sizeof(RsPlan) * ns);
+    if (!r) r = grow(b, (void **)&b->rs_cnt, &b->rs_cnt_cap, sizeof(int32_t) * ns);
+    if (!r) r = grow(b, (void **)&b->rs_tab, &b->rs_tab_cap, sizeof(float) * tab.size());
+    if (r) {
+        rs_free(b);
+        return r;
+    }
+    HIPCHK(hipMemcpyAsync(b->rs_dcfg, &cfg, sizeof(cfg), hipMemcpyHostToDevice, b->own));
+    HIPCHK(hipMemcpyAsync(b->rs_tab, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice, b->own));
+    /* a change of the output format restarts every stream's resampler */
+    HIPCHK(hipMemsetAsync(b->rs_st, 0, sizeof(RsState) * ns, b->own));
+    HIPCHK(hipStreamSynchronize(b->own));
+    b->rs_cfg = cfg;
+    b->rs_hz = out_hz;
+    b->rs_ch = out_channels;
+    b->rs_timed = false;
+    return MP3D_OK;
+}
+
+extern "C" int mp3d_batch_decode_packed(mp3d_batch *b, const uint8_t *frames, const uint64_t *offsets,
+                                        const uint32_t *sizes, int n, int F, void *out, int f32, long long out_stride,
+                                        int *out_count, int flags, mp3d_frame_info *infos, void *hip_stream) {
+    if (!b || !b->rs_hz || !out || !out_count || out_stride < 0 || (flags & ~MP3D_PACK_FLUSH)) return MP3D_E_ARG;
+    if (!frames || !offsets || !sizes || n <= 0 || F <= 0) return MP3D_E_ARG;
+    if (n > b->max_streams || F > b->max_frames) return MP3D_E_CAPACITY;
+    HIPCHK(hipSetDevice(b->device));
+    const int oc = b->rs_ch;
+    const size_t eb = f32 ? sizeof(float) : sizeof(int16_t);
+    /* blocks per stream: enough tiles for the longest output any input rate
+     * can produce within the stride */
+    const long long stride = std::min<long long>(out_stride, mp3d_packed_max_samples(b->rs_hz, F, 0));
+    long long tiles = 1;
+    for (int i = 0; i < MP3D_RS_RATES; i++) {
+        const long long most = std::min(stride, rs_bound(RS_RATES[i], b->rs_hz, F));
+        tiles = std::max(tiles, (most + b->rs_cfg.f[i].tile - 1) / b->rs_cfg.f[i].tile);
+    }
+    if (tiles * n > 0x7fffffffLL) return MP3D_E_CAPACITY;
+    /* the kernel stores one sample frame (all channels) per instruction: a
+     * device sink must be aligned to it (a host sink is filled by copies) */
+    if (is_device_ptr(out, b->device) && (uintptr_t)out % (eb * oc)) return MP3D_E_ARG;
+    int r = grow(b, (void **)&b->rs_rows, &b->rs_rows_cap, sizeof(float) * 2304 * (size_t)n * F);
+    if (!r) r = grow(b, (void **)&b->rs_prefix, &b->rs_prefix_cap, sizeof(int32_t) * (size_t)n * (F + 1));
+    const bool out_dev = is_device_ptr(out, b->device), cnt_dev = is_device_ptr(out_count, b->device);
+    if (!r && !out_dev) r = grow(b, &b->rs_out, &b->rs_out_cap, eb * oc * (size_t)stride * n + 16);
+    if (r) return r;
+    /* the decode itself: the float32 path into the handle's rows */
+    r = batch_decode(b, frames, offsets, sizes, n, F, b->rs_rows, true, infos, hip_stream, false);
+    if (r) return r;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : b->own;
+    CallEnd done{b, s};
+    const mp3d_frame_info *dinf = infos && is_device_ptr(infos, b->device) ? infos : b->d_infos;
+    void *dout = out_dev ? out : b->rs_out;
+    int32_t *dcnt = cnt_dev ? (int32_t *)out_count : b->rs_cnt;
+    if (b->timing) HIPCHK(hipEventRecord(b->ev_rs[0], s));
+    if (b->poison) launch_lds_poison(g_dev[b->device].n_cu, s);
+    launch_resample(b->rs_rows, dinf, b->rs_st, b->rs_dcfg, oc, b->rs_tab, b->rs_plan, b->rs_prefix, dout, f32 != 0, dcnt,
+                    n, F, out_dev ? out_stride : stride, (int)tiles, (flags & MP3D_PACK_FLUSH) ? 1 : 0, s);
+    if (b->timing) {
+        HIPCHK(hipEventRecord(b->ev_rs[1], s));
+        b->rs_timed = true;
+    }
+    HIPCHK(hipGetLastError());
+    if (out_dev && cnt_dev) return MP3D_OK;
+    std::vector<int32_t> hc((size_t)n);
+    HIPCHK(hipMemcpyAsync(hc.data(), dcnt, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (!out_dev) {
+        /* only each stream's own samples reach the caller's buffer; the
+         * caller's stride is its own, the staging buffer's is `stride` */
+        for (int i = 0; i < n; i++)
+            if (hc[i] > 0)
+                HIPCHK(hipMemcpyAsync((uint8_t *)out + eb * oc * (size_t)out_stride * i,
+                                      (const uint8_t *)dout + eb * oc * (size_t)stride * i, eb * oc * (size_t)hc[i],
+                                      hipMemcpyDefault, s));
+    }
+    if (!cnt_dev) HIPCHK(hipMemcpyAsync(out_count, hc.data(), sizeof(int32_t) * n, hipMemcpyDefault, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return MP3D_OK;
+}
+
+extern "C" int mp3d_batch_resample_time(mp3d_batch *b, float *us) {
+    if (!b || !us || !b->timing || !b->rs_timed) return MP3D_E_ARG;
+    HIPCHK(hipEventSynchronize(b->ev_rs[1]));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, b->ev_rs[0], b->ev_rs[1]));
+    *us = ms * 1000.f;
     return MP3D_OK;
 }
 

@@ -1,0 +1,64 @@
+/*
+ * mp3d_resample.h -- data layout of the packed uniform-rate PCM sink, shared
+ * by mp3d_resample.hip and the host library ("Packed PCM sink").
+ *
+ * A packed call decodes float32 rows [n][F][2304] into a handle-owned buffer
+ * and then runs three kernels on them:
+ *   k_rs_plan    thread / stream : input count, first output, output count
+ *   k_rs_filter  block / (stream, output tile) : channel map + polyphase FIR
+ *   k_rs_update  block / stream  : history and position for the next call
+ */
+#ifndef MP3D_RESAMPLE_H
+#define MP3D_RESAMPLE_H
+
+#include <stdint.h>
+
+#define MP3D_RS_RATES 9
+#define MP3D_RS_MAX_TAPS 288  /* 48 kHz -> 8 kHz */
+#define MP3D_RS_HIST 288      /* history samples kept per channel (>= taps - 1) */
+#define MP3D_RS_SPAN 4096     /* input samples per channel one filter block stages */
+#define MP3D_RS_THREADS 256
+#define MP3D_RS_UP_TAPS 48    /* taps per phase of every upsampling filter */
+
+/* Per-stream resampler state (one per stream slot of the handle; NOT part of
+ * the StreamState blob).  All zero = restarted. */
+struct RsState {
+    int32_t rate_i;  /* 1 + index of the stream's input rate; 0: none yet      */
+    int32_t pad_;
+    /* input samples since the restart, reduced by multiples of M once past
+     * post + M (outputs then shift by multiples of L: every relative index
+     * and phase is unchanged), so it never grows                             */
+    int64_t pos;
+    float hist[MP3D_RS_HIST * 2]; /* last pre + post channel-mapped inputs,
+                                   * interleaved by output channel, oldest first */
+};
+
+/* One polyphase filter of the handle's output rate (input rate index i). */
+struct RsFilt {
+    int32_t L, M, T;   /* phases, decimation, taps per phase (1, 1, 1: bypass)  */
+    int32_t Tp;        /* device row stride in floats (T rounded up to 4)       */
+    int32_t pre, post; /* inputs before / after n0 an output reads              */
+    int32_t off;       /* float offset of taps[L][Tp] in the device table       */
+    int32_t tile;      /* outputs per filter block                              */
+    int32_t S;         /* output stride of one thread: a multiple of L when the
+                        * taps stay in registers (T == 48), else the block size */
+};
+
+struct RsCfg {
+    RsFilt f[MP3D_RS_RATES];
+    int32_t out_ch;
+};
+
+/* Per-stream plan of one call (k_rs_plan -> k_rs_filter, k_rs_update). */
+struct RsPlan {
+    int64_t pos;     /* state position at the call's start                     */
+    int64_t m0;      /* first output index of the call                         */
+    int32_t rate_i;  /* 1 + input rate index, 0: the stream has no audio yet   */
+    int32_t n_in;    /* input samples of the call                              */
+    int32_t count;   /* outputs of the call; -1: over the stride               */
+    int32_t restart; /* the state restarts after the call (flush, overflow)    */
+};
+
+/* prefix[s * (F + 1) + f]: input samples of the call before frame f */
+
+#endif

@@ -1,0 +1,328 @@
+/*
+ * mp3d_resample.hip -- the packed uniform-rate PCM sink: channel map and
+ * polyphase resampling of a call's float32 rows into contiguous samples per
+ * stream at one rate and channel count ("Packed PCM sink").
+ *
+ * Output m of a stream is  y[m] = sum_j taps[p][j] * x[n0 - pre + j],
+ * n0 = floor(m M / L), p = (m M) mod L, accumulated by ONE float32 FMA chain
+ * in ascending j whatever thread, tile or call computes it; inputs before the
+ * stream start, and after its end in a flushed call, are staged as zeros so
+ * the chain has the same length everywhere.
+ *
+ * Mapping (k_rs_filter): one 256-thread block per (stream, output tile).  The
+ * block stages the tile's input span -- history, then the rows' samples with
+ * the channel map applied, interleaved by output channel -- into LDS.
+ *  - Upsampling (48 taps per phase, up to 1 280 phases, the phases of
+ *    consecutive outputs scattered over the table): a thread walks outputs
+ *    m, m + S, m + 2S ... with S a multiple of L, so its phase never changes
+ *    and its 48 taps are loaded into registers once per pass (S / 256 passes
+ *    per tile, each load serving tile / S outputs: 3 to 4 at 44.1 -> 48 kHz,
+ *    DESIGN.md section 4b); lanes hold consecutive
+ *    m, so their LDS reads are (nearly) consecutive and their stores coalesce.
+ *  - Downsampling (54 .. 288 taps): a thread walks m, m + 256 ...; the taps
+ *    come from the table (at most 87 KB per rate pair, L2 / L1 resident) in
+ *    16-byte loads of its phase's row, 4 FMAs per channel for each.
+ *  - Equal rates: the staged samples are copied.
+ */
+#include "mp3d_device.h"
+#include "mp3d_resample.h"
+
+namespace mp3d {
+
+__device__ __forceinline__ int rs_rate_index(int hz) {
+    const int R[MP3D_RS_RATES] = {8000, 11025, 12000, 16000, 22050, 24000, 32000, 44100, 48000};
+    int k = -1;
+#pragma unroll
+    for (int i = 0; i < MP3D_RS_RATES; i++) k = hz == R[i] ? i : k;
+    return k;
+}
+
+__device__ __forceinline__ long long rs_ceil_div(long long a, long long b) { return (a + b - 1) / b; }
+
+/* outputs emitted once n inputs were seen: those with n0 + post <= n - 1 */
+__device__ __forceinline__ long long rs_emitted(long long n, const RsFilt &f) {
+    return n > f.post ? rs_ceil_div((n - f.post) * f.L, f.M) : 0;
+}
+
+__global__ void __launch_bounds__(MP3D_RS_THREADS)
+k_rs_plan(const DevInfo *__restrict__ inf, const RsState *__restrict__ st, const RsCfg *__restrict__ cfg, RsPlan *__restrict__ plan,
+          int32_t *__restrict__ prefix, int32_t *__restrict__ out_count, int n, int F, long long stride, int flush) {
+    const int s = blockIdx.x * MP3D_RS_THREADS + threadIdx.x;
+    if (s >= n) return;
+    int ri = st[s].rate_i;
+    const long long pos = ri ? st[s].pos : 0;
+    int nin = 0;
+    int32_t *pf = prefix + (size_t)s * (F + 1);
+    for (int f = 0; f < F; f++) {
+        const DevInfo d = inf[(size_t)s * F + f];
+        pf[f] = nin;
+        if (d.samples > 0 && d.samples <= 1152 && (d.channels == 1 || d.channels == 2)) {
+            if (!ri) ri = rs_rate_index(d.hz) + 1;
+            if (ri) nin += d.samples;
+        }
+    }
+    pf[F] = nin;
+    RsPlan P;
+    P.pos = pos;
+    P.m0 = 0;
+    P.rate_i = ri;
+    P.n_in = nin;
+    P.count = 0;
+    P.restart = flush;
+    if (ri) {
+        const RsFilt f = cfg->f[ri - 1];
+        const long long n1 = pos + nin;
+        P.m0 = rs_emitted(pos, f);
+        const long long m1 = flush ? rs_ceil_div(n1 * f.L, f.M) : rs_emitted(n1, f);
+        const long long c = m1 - P.m0;
+        if (c > stride) {
+            P.count = -1;
+            P.restart = 1;
+        } else {
+            P.count = (int)c;
+        }
+    }
+    plan[s] = P;
+    out_count[s] = P.count;
+}
+
+/* sample k of a row with ch channels, mapped to OC channels */
+template <int OC>
+__device__ __forceinline__ void rs_load(const float *__restrict__ row, int ch, int k, float *v) {
+    if (ch == 2) {
+        const float2 a = *(const float2 *)(row + 2 * k);
+        if (OC == 2) {
+            v[0] = a.x;
+            v[1] = a.y;
+        } else {
+            v[0] = 0.5f * (a.x + a.y);
+        }
+    } else {
+        const float a = row[k];
+        v[0] = a;
+        if (OC == 2) v[1] = a;
+    }
+}
+
+/* the frame holding input sample rel (0 <= rel < prefix[F]): the last f with
+ * prefix[f] <= rel */
+__device__ __forceinline__ int rs_frame_of(const int32_t *__restrict__ pf, int F, int rel) {
+    int lo = 0, hi = F; /* prefix[lo] <= rel < prefix[hi] */
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (pf[mid] <= rel) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+template <int OC, bool F32>
+__device__ __forceinline__ void rs_store(void *__restrict__ out, size_t at, const float *acc) {
+    if (F32) {
+        if (OC == 2) *(float2 *)((float *)out + at) = make_float2(acc[0], acc[1]);
+        else ((float *)out)[at] = acc[0];
+    } else {
+        /* the library's int16 rounding: clamp(floor(y * 32768 + 0.5)) of the
+         * exact sum (v + 0.5f itself could round up across an integer): the
+         * scaling and v - floor(v) are exact */
+        short q[OC];
+#pragma unroll
+        for (int c = 0; c < OC; c++) {
+            const float v = acc[c] * 32768.0f, fl = floorf(v);
+            const float r = v - fl >= 0.5f ? fl + 1.0f : fl;
+            q[c] = (short)fminf(fmaxf(r, -32768.0f), 32767.0f);
+        }
+        if (OC == 2) *(short2 *)((short *)out + at) = make_short2(q[0], q[1]);
+        else ((short *)out)[at] = q[0];
+    }
+}
+
+template <int OC, bool F32>
+__global__ void __launch_bounds__(MP3D_RS_THREADS)
+k_rs_filter(const float *__restrict__ rows, const DevInfo *__restrict__ inf, const RsState *__restrict__ st,
+            const RsCfg *__restrict__ cfg, const float *__restrict__ tab, const RsPlan *__restrict__ plan,
+            const int32_t *__restrict__ prefix, void *__restrict__ out, int F, long long stride, int tiles) {
+    __shared__ __attribute__((aligned(16))) float sx[(MP3D_RS_SPAN + 8) * OC];
+    const int s = blockIdx.x / tiles, tile = blockIdx.x % tiles, t = threadIdx.x;
+    const RsPlan P = plan[s];
+    if (P.count <= 0) return;
+    const RsFilt f = cfg->f[P.rate_i - 1];
+    const long long mA = (long long)tile * f.tile;
+    if (mA >= P.count) return;
+    const int mB = (int)min((long long)P.count, mA + f.tile); /* outputs [mA, mB) of the call */
+    /* input span [nA, nB) of the tile, relative to the call's first sample */
+    const int relA = (int)(((P.m0 + mA) * f.M) / f.L - f.pre - P.pos);
+    const int relB = (int)(((P.m0 + mB - 1) * f.M) / f.L + f.post + 1 - P.pos);
+    const int len = min(relB - relA, MP3D_RS_SPAN); /* <= SPAN by the choice of f.tile */
+    const int HL = f.pre + f.post;
+    const float *hist = st[s].hist;
+    /* history before the call's samples, zeros after them (a flushed call) */
+    for (int i = t; i < len; i += MP3D_RS_THREADS) {
+        const int rel = relA + i;
+        if (rel >= 0 && rel < P.n_in) continue;
+#pragma unroll
+        for (int c = 0; c < OC; c++) sx[i * OC + c] = rel < 0 && HL + rel >= 0 ? hist[(HL + rel) * OC + c] : 0.0f;
+    }
+    const int lo = max(relA, 0), hi = min(relA + len, P.n_in);
+    if (lo < hi) {
+        const int32_t *pf = prefix + (size_t)s * (F + 1);
+        for (int fr = rs_frame_of(pf, F, lo); fr < F; fr++) {
+            const int a = pf[fr], b = pf[fr + 1];
+            if (a >= hi) break;
+            if (b <= a) continue;
+            const int ch = inf[(size_t)s * F + fr].channels;
+            const float *row = rows + ((size_t)s * F + fr) * 2304;
+            for (int k = max(a, lo) + t; k < min(b, hi); k += MP3D_RS_THREADS) {
+                float v[OC];
+                rs_load<OC>(row, ch, k - a, v);
+#pragma unroll
+                for (int c = 0; c < OC; c++) sx[(k - relA) * OC + c] = v[c];
+            }
+        }
+    }
+    __syncthreads();
+    const size_t obase = (size_t)s * (size_t)stride * OC;
+    if (f.T == 1) { /* equal rates: copy */
+        for (int mo = (int)mA + t; mo < mB; mo += MP3D_RS_THREADS) {
+            const int xi = (int)(P.m0 + mo - P.pos) - relA;
+            float acc[OC];
+#pragma unroll
+            for (int c = 0; c < OC; c++) acc[c] = sx[xi * OC + c];
+            rs_store<OC, F32>(out, obase + (size_t)mo * OC, acc);
+        }
+        return;
+    }
+    const float *ft = tab + f.off;
+    if (f.T == MP3D_RS_UP_TAPS) {
+        /* one phase per thread and pass: f.S is a multiple of L */
+        const int step = (int)((long long)f.S * f.M / f.L);
+        for (int r = t; r < f.S; r += MP3D_RS_THREADS) {
+            if (mA + r >= mB) break;
+            const long long mm = (P.m0 + mA + r) * f.M;
+            const int p = (int)(mm % f.L);
+            int xi = (int)(mm / f.L - f.pre - P.pos) - relA;
+            float4 tp[MP3D_RS_UP_TAPS / 4];
+#pragma unroll
+            for (int j = 0; j < MP3D_RS_UP_TAPS / 4; j++) tp[j] = *(const float4 *)(ft + (size_t)p * f.Tp + 4 * j);
+            for (int mo = (int)mA + r; mo < mB; mo += f.S, xi += step) {
+                float acc[OC];
+#pragma unroll
+                for (int c = 0; c < OC; c++) acc[c] = 0.0f;
+                const float *x = sx + xi * OC;
+#pragma unroll
+                for (int j = 0; j < MP3D_RS_UP_TAPS / 4; j++) {
+                    const float w[4] = {tp[j].x, tp[j].y, tp[j].z, tp[j].w};
+#pragma unroll
+                    for (int q = 0; q < 4; q++)
+#pragma unroll
+                        for (int c = 0; c < OC; c++) acc[c] = fmaf(w[q], x[(4 * j + q) * OC + c], acc[c]);
+                }
+                rs_store<OC, F32>(out, obase + (size_t)mo * OC, acc);
+            }
+        }
+        return;
+    }
+    /* general: consecutive outputs on consecutive threads, taps from the table */
+    if (mA + t >= mB) return;
+    const long long mm = (P.m0 + mA + t) * f.M;
+    int p = (int)(mm % f.L);
+    int xi = (int)(mm / f.L - f.pre - P.pos) - relA;
+    const int dq = (int)((long long)MP3D_RS_THREADS * f.M / f.L), dr = (int)((long long)MP3D_RS_THREADS * f.M % f.L);
+    const int T4 = f.T & ~3;
+    for (int mo = (int)mA + t; mo < mB; mo += MP3D_RS_THREADS) {
+        float acc[OC];
+#pragma unroll
+        for (int c = 0; c < OC; c++) acc[c] = 0.0f;
+        const float *x = sx + xi * OC;
+        const float *w = ft + (size_t)p * f.Tp;
+        for (int j = 0; j < T4; j += 4) {
+            const float4 w4 = *(const float4 *)(w + j);
+            const float wq[4] = {w4.x, w4.y, w4.z, w4.w};
+#pragma unroll
+            for (int q = 0; q < 4; q++)
+#pragma unroll
+                for (int c = 0; c < OC; c++) acc[c] = fmaf(wq[q], x[(j + q) * OC + c], acc[c]);
+        }
+        for (int j = T4; j < f.T; j++)
+#pragma unroll
+            for (int c = 0; c < OC; c++) acc[c] = fmaf(w[j], x[j * OC + c], acc[c]);
+        rs_store<OC, F32>(out, obase + (size_t)mo * OC, acc);
+        xi += dq;
+        p += dr;
+        if (p >= f.L) {
+            p -= f.L;
+            xi++;
+        }
+    }
+}
+
+/* the state after the call: the last pre + post inputs, the position */
+template <int OC>
+__global__ void __launch_bounds__(MP3D_RS_THREADS)
+k_rs_update(const float *__restrict__ rows, const DevInfo *__restrict__ inf, RsState *__restrict__ st,
+            const RsCfg *__restrict__ cfg, const RsPlan *__restrict__ plan, const int32_t *__restrict__ prefix, int F) {
+    __shared__ float nh[MP3D_RS_HIST * OC];
+    const int s = blockIdx.x, t = threadIdx.x;
+    const RsPlan P = plan[s];
+    RsState *S = st + s;
+    if (P.restart) {
+        for (int i = t; i < MP3D_RS_HIST * 2; i += MP3D_RS_THREADS) S->hist[i] = 0.0f;
+        if (t == 0) {
+            S->rate_i = 0;
+            S->pad_ = 0;
+            S->pos = 0;
+        }
+        return;
+    }
+    if (!P.rate_i || !P.n_in) return;
+    const RsFilt f = cfg->f[P.rate_i - 1];
+    const int HL = f.pre + f.post;
+    const int32_t *pf = prefix + (size_t)s * (F + 1);
+    for (int i = t; i < HL; i += MP3D_RS_THREADS) {
+        const int rel = P.n_in - HL + i;
+        float v[OC];
+        if (rel < 0) {
+#pragma unroll
+            for (int c = 0; c < OC; c++) v[c] = S->hist[(HL + rel) * OC + c];
+        } else {
+            const int fr = rs_frame_of(pf, F, rel);
+            rs_load<OC>(rows + ((size_t)s * F + fr) * 2304, inf[(size_t)s * F + fr].channels, rel - pf[fr], v);
+        }
+#pragma unroll
+        for (int c = 0; c < OC; c++) nh[i * OC + c] = v[c];
+    }
+    __syncthreads();
+    for (int i = t; i < HL * OC; i += MP3D_RS_THREADS) S->hist[i] = nh[i];
+    if (t == 0) {
+        long long pos = P.pos + P.n_in;
+        if (pos >= (long long)f.post + f.M) pos = f.post + (pos - f.post) % f.M;
+        S->rate_i = P.rate_i;
+        S->pos = pos;
+    }
+}
+
+void launch_resample(const float *rows, const void *infos, RsState *st, const RsCfg *cfg, int out_ch, const float *tab,
+                     RsPlan *plan, int32_t *prefix, void *out, bool f32, int32_t *out_count, int n, int F,
+                     long long stride, int tiles, int flush, hipStream_t strm) {
+    const DevInfo *inf = (const DevInfo *)infos;
+    hipLaunchKernelGGL(k_rs_plan, dim3((n + MP3D_RS_THREADS - 1) / MP3D_RS_THREADS), dim3(MP3D_RS_THREADS), 0, strm, inf,
+                       st, cfg, plan, prefix, out_count, n, F, stride, flush);
+    const dim3 grid((unsigned)n * (unsigned)tiles), blk(MP3D_RS_THREADS);
+#define RS_FILTER(OC, F32)                                                                                             \
+    hipLaunchKernelGGL((k_rs_filter<OC, F32>), grid, blk, 0, strm, rows, inf, st, cfg, tab, plan, prefix, out, F, stride, \
+                       tiles)
+    if (out_ch == 2) {
+        if (f32) RS_FILTER(2, true);
+        else RS_FILTER(2, false);
+    } else {
+        if (f32) RS_FILTER(1, true);
+        else RS_FILTER(1, false);
+    }
+#undef RS_FILTER
+    if (out_ch == 2)
+        hipLaunchKernelGGL(k_rs_update<2>, dim3(n), blk, 0, strm, rows, inf, st, cfg, plan, prefix, F);
+    else
+        hipLaunchKernelGGL(k_rs_update<1>, dim3(n), blk, 0, strm, rows, inf, st, cfg, plan, prefix, F);
+}
+
+} // namespace mp3d
