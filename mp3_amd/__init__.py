@@ -9,7 +9,10 @@ player's per-frame decode call):
 
 The compute path is the HIP library mp3_amd/libmp3d.so; there is no CPU
 fallback.  Importing works without a GPU; creating a decoder does not.
+library(path) selects another build of the library (the tests' debug build
+libmp3d_wglds.so) for the decoders created inside the block.
 """
+import contextlib
 import ctypes
 import os
 import pathlib
@@ -64,64 +67,95 @@ class MP3DError(RuntimeError):
     pass
 
 
+def _bind(L):
+    """Argument and result types of every export, on one loaded build."""
+    vp, i, u64p, u32p = ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p
+    L.mp3d_dec_create.argtypes = [ctypes.POINTER(vp)]
+    L.mp3d_dec_create_on.argtypes = [i, ctypes.POINTER(vp)]
+    L.mp3d_dec_destroy.argtypes = [vp]
+    L.mp3d_dec_destroy.restype = None
+    L.mp3d_dec_reset.argtypes = [vp]
+    L.mp3d_dec_reset.restype = None
+    L.mp3d_decode_frame.argtypes = [vp, ctypes.c_char_p, ctypes.c_size_t, vp, ctypes.POINTER(FrameInfo)]
+    L.mp3d_batch_create.argtypes = [i, i, i, ctypes.POINTER(vp)]
+    L.mp3d_batch_destroy.argtypes = [vp]
+    L.mp3d_batch_destroy.restype = None
+    L.mp3d_batch_reset.argtypes = [vp]
+    L.mp3d_batch_decode.argtypes = [vp, vp, u64p, u32p, i, i, vp, vp, vp]
+    L.mp3d_batch_decode_f32.argtypes = [vp, vp, u64p, u32p, i, i, vp, vp, vp]
+    L.mp3d_decode_frame_f32.argtypes = [vp, ctypes.c_char_p, ctypes.c_size_t, vp, ctypes.POINTER(FrameInfo)]
+    L.mp3d_batch_sync.argtypes = [vp]
+    L.mp3d_batch_huffman_only.argtypes = [vp, vp, u64p, u32p, i, i, vp, vp, vp]
+    L.mp3d_batch_synth_only.argtypes = [vp, vp, vp, vp, i, i, i, i, vp, vp]
+    L.mp3d_strerror.argtypes = [i]
+    L.mp3d_strerror.restype = ctypes.c_char_p
+    L.mp3d_batch_set_timing.argtypes = [vp, i]
+    L.mp3d_batch_kernel_times.argtypes = [vp, vp]
+    L.mp3d_batch_stream_info.argtypes = [vp, i, vp]
+    L.mp3d_dec_stream_info.argtypes = [vp, ctypes.POINTER(StreamInfo)]
+    L.mp3d_batch_decode_long.argtypes = [vp, vp, ctypes.c_size_t, i, vp, i, ctypes.c_longlong, vp,
+                                         ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(StreamInfo)]
+    L.mp3d_long_plan.argtypes = [ctypes.c_char_p, ctypes.c_size_t, i, ctypes.c_longlong, vp, vp,
+                                 ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_int)]
+    L.mp3d_batch_set_options.argtypes = [vp, i]
+    L.mp3d_dec_set_options.argtypes = [vp, i]
+    L.mp3d_decode_frame_ex.argtypes = [vp, ctypes.c_char_p, ctypes.c_size_t, vp, i, ctypes.POINTER(FrameInfo)]
+    L.mp3d_state_bytes.restype = ctypes.c_size_t
+    L.mp3d_batch_get_state.argtypes = [vp, i, i, vp]
+    L.mp3d_batch_set_state.argtypes = [vp, i, i, vp]
+    L.mp3d_dec_get_state.argtypes = [vp, vp]
+    L.mp3d_dec_set_state.argtypes = [vp, vp]
+    ip = ctypes.POINTER(ctypes.c_int)
+    L.mp3d_resample_filter.argtypes = [i, i, ip, ip, ip, vp, ctypes.c_size_t]
+    L.mp3d_resample_filter.restype = ctypes.c_longlong
+    L.mp3d_batch_set_output.argtypes = [vp, i, i]
+    L.mp3d_packed_max_samples.argtypes = [i, i, i]
+    L.mp3d_packed_max_samples.restype = ctypes.c_longlong
+    L.mp3d_batch_decode_packed.argtypes = [vp, vp, u64p, u32p, i, i, vp, i, ctypes.c_longlong, vp, i, vp, vp]
+    L.mp3d_batch_resample_time.argtypes = [vp, vp]
+    if hasattr(L, "mp3d_debug_wglds_probe"):  # libmp3d_wglds.so only (tests/test_gpu_wglds.py)
+        L.mp3d_debug_wglds_probe.argtypes = [i, i, vp, i]
+    return L
+
+
+_loaded = {}  # path -> CDLL: one copy of a build per process
+
+
+def _load(path):
+    path = pathlib.Path(path).resolve()
+    if path not in _loaded:
+        if not path.exists():
+            raise ImportError("mp3_amd: %s missing -- run __graft_entry__.build() (no CPU fallback exists)" % path)
+        _loaded[path] = _bind(ctypes.CDLL(str(path)))
+    return _loaded[path]
+
+
 def lib():
-    """Load libmp3d.so (fails loudly if it was not built)."""
+    """The current build of the library: libmp3d.so (or MP3D_LIB) unless
+    inside library().  Fails loudly if it was not built."""
     global _lib
     if _lib is None:
-        if not LIB_PATH.exists():
-            raise ImportError("mp3_amd: %s missing -- run __graft_entry__.build() (no CPU fallback exists)" % LIB_PATH)
-        L = ctypes.CDLL(str(LIB_PATH))
-        vp, i, u64p, u32p = ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p
-        L.mp3d_dec_create.argtypes = [ctypes.POINTER(vp)]
-        L.mp3d_dec_create_on.argtypes = [i, ctypes.POINTER(vp)]
-        L.mp3d_dec_destroy.argtypes = [vp]
-        L.mp3d_dec_destroy.restype = None
-        L.mp3d_dec_reset.argtypes = [vp]
-        L.mp3d_dec_reset.restype = None
-        L.mp3d_decode_frame.argtypes = [vp, ctypes.c_char_p, ctypes.c_size_t, vp, ctypes.POINTER(FrameInfo)]
-        L.mp3d_batch_create.argtypes = [i, i, i, ctypes.POINTER(vp)]
-        L.mp3d_batch_destroy.argtypes = [vp]
-        L.mp3d_batch_destroy.restype = None
-        L.mp3d_batch_reset.argtypes = [vp]
-        L.mp3d_batch_decode.argtypes = [vp, vp, u64p, u32p, i, i, vp, vp, vp]
-        L.mp3d_batch_decode_f32.argtypes = [vp, vp, u64p, u32p, i, i, vp, vp, vp]
-        L.mp3d_decode_frame_f32.argtypes = [vp, ctypes.c_char_p, ctypes.c_size_t, vp, ctypes.POINTER(FrameInfo)]
-        L.mp3d_batch_sync.argtypes = [vp]
-        L.mp3d_batch_huffman_only.argtypes = [vp, vp, u64p, u32p, i, i, vp, vp, vp]
-        L.mp3d_batch_synth_only.argtypes = [vp, vp, vp, vp, i, i, i, i, vp, vp]
-        L.mp3d_strerror.argtypes = [i]
-        L.mp3d_strerror.restype = ctypes.c_char_p
-        L.mp3d_batch_set_timing.argtypes = [vp, i]
-        L.mp3d_batch_kernel_times.argtypes = [vp, vp]
-        L.mp3d_batch_stream_info.argtypes = [vp, i, vp]
-        L.mp3d_dec_stream_info.argtypes = [vp, ctypes.POINTER(StreamInfo)]
-        L.mp3d_batch_decode_long.argtypes = [vp, vp, ctypes.c_size_t, i, vp, i, ctypes.c_longlong, vp,
-                                             ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(StreamInfo)]
-        L.mp3d_long_plan.argtypes = [ctypes.c_char_p, ctypes.c_size_t, i, ctypes.c_longlong, vp, vp,
-                                     ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_int)]
-        L.mp3d_batch_set_options.argtypes = [vp, i]
-        L.mp3d_dec_set_options.argtypes = [vp, i]
-        L.mp3d_decode_frame_ex.argtypes = [vp, ctypes.c_char_p, ctypes.c_size_t, vp, i, ctypes.POINTER(FrameInfo)]
-        L.mp3d_state_bytes.restype = ctypes.c_size_t
-        L.mp3d_batch_get_state.argtypes = [vp, i, i, vp]
-        L.mp3d_batch_set_state.argtypes = [vp, i, i, vp]
-        L.mp3d_dec_get_state.argtypes = [vp, vp]
-        L.mp3d_dec_set_state.argtypes = [vp, vp]
-        ip = ctypes.POINTER(ctypes.c_int)
-        L.mp3d_resample_filter.argtypes = [i, i, ip, ip, ip, vp, ctypes.c_size_t]
-        L.mp3d_resample_filter.restype = ctypes.c_longlong
-        L.mp3d_batch_set_output.argtypes = [vp, i, i]
-        L.mp3d_packed_max_samples.argtypes = [i, i, i]
-        L.mp3d_packed_max_samples.restype = ctypes.c_longlong
-        L.mp3d_batch_decode_packed.argtypes = [vp, vp, u64p, u32p, i, i, vp, i, ctypes.c_longlong, vp, i, vp, vp]
-        L.mp3d_batch_resample_time.argtypes = [vp, vp]
-        _lib = L
+        _lib = _load(LIB_PATH)
     return _lib
 
 
-def _check(rc):
+@contextlib.contextmanager
+def library(path):
+    """Make lib() return the build at `path` inside the block (a debug build
+    next to the product in one process).  A Decoder / BatchDecoder keeps the
+    build that created its handle for every later call, whatever is current
+    then; the module-level functions use the current one."""
+    global _lib
+    prev, _lib = _lib, _load(path)
+    try:
+        yield _lib
+    finally:
+        _lib = prev
+
+
+def _check(rc, L=None):
     if rc < 0:
-        L = lib()
+        L = L or lib()
         raise MP3DError("mp3d error %d (%s), hip error %d" % (rc, L.mp3d_strerror(rc).decode(), L.mp3d_last_hip_error()))
     return rc
 
@@ -148,27 +182,30 @@ class Decoder:
     """Per-frame decoder (mp3d_decode_frame), one per stream."""
 
     def __init__(self, device=None):
-        L = lib()
+        L = self._L = lib()  # the build that owns the handle: every later call goes to it
         h = ctypes.c_void_p()
         if device is None:
-            _check(L.mp3d_dec_create(ctypes.byref(h)))
+            _check(L.mp3d_dec_create(ctypes.byref(h)), L)
         else:
-            _check(L.mp3d_dec_create_on(int(device), ctypes.byref(h)))
+            _check(L.mp3d_dec_create_on(int(device), ctypes.byref(h)), L)
         self._h = h
+
+    def _ck(self, rc):
+        return _check(rc, self._L)
 
     def close(self):
         if getattr(self, "_h", None):
-            lib().mp3d_dec_destroy(self._h)
+            self._L.mp3d_dec_destroy(self._h)
             self._h = None
 
     __del__ = close
 
     def reset(self):
-        lib().mp3d_dec_reset(self._h)
+        self._L.mp3d_dec_reset(self._h)
 
     def set_options(self, flags):
         """MP3D_OPT_* flags (OPT_CRC_CHECK) for later decode calls."""
-        _check(lib().mp3d_dec_set_options(self._h, int(flags)))
+        self._ck(self._L.mp3d_dec_set_options(self._h, int(flags)))
 
     def decode_frame(self, buf, f32=False, last=False):
         """Returns (samples_per_channel, pcm [samples*channels], FrameInfo);
@@ -179,25 +216,25 @@ class Decoder:
         info = FrameInfo()
         buf = bytes(buf)
         flags = (FRAME_F32 if f32 else 0) | (FRAME_LAST if last else 0)
-        n = _check(lib().mp3d_decode_frame_ex(self._h, buf, len(buf), pcm.ctypes.data, flags, ctypes.byref(info)))
+        n = self._ck(self._L.mp3d_decode_frame_ex(self._h, buf, len(buf), pcm.ctypes.data, flags, ctypes.byref(info)))
         return n, pcm[: n * max(info.channels, 1)], info
 
     def get_state(self):
         """Opaque decoder state (np.uint8 [state_bytes()]) for set_state."""
         buf = np.zeros(state_bytes(), np.uint8)
-        _check(lib().mp3d_dec_get_state(self._h, buf.ctypes.data))
+        self._ck(self._L.mp3d_dec_get_state(self._h, buf.ctypes.data))
         return buf
 
     def set_state(self, buf):
         buf = np.ascontiguousarray(buf, np.uint8)
         if buf.size != state_bytes():
             raise ValueError("state blob of %d bytes, expected %d" % (buf.size, state_bytes()))
-        _check(lib().mp3d_dec_set_state(self._h, buf.ctypes.data))
+        self._ck(self._L.mp3d_dec_set_state(self._h, buf.ctypes.data))
 
     def stream_info(self):
         """StreamInfo of the stream decoded so far (Xing/Info tag, gapless)."""
         info = StreamInfo()
-        _check(lib().mp3d_dec_stream_info(self._h, ctypes.byref(info)))
+        self._ck(self._L.mp3d_dec_stream_info(self._h, ctypes.byref(info)))
         return info
 
     def decode_stream(self, data, gapless=False, f32=False):
@@ -228,36 +265,39 @@ class BatchDecoder:
     """Batched decoder: per-stream state stays in HBM across calls."""
 
     def __init__(self, max_streams, max_frames, device=0):
-        L = lib()
+        L = self._L = lib()  # the build that owns the handle: every later call goes to it
         h = ctypes.c_void_p()
-        _check(L.mp3d_batch_create(int(device), int(max_streams), int(max_frames), ctypes.byref(h)))
+        _check(L.mp3d_batch_create(int(device), int(max_streams), int(max_frames), ctypes.byref(h)), L)
         self._h = h
         self.device = device
         self.max_streams, self.max_frames = max_streams, max_frames
 
+    def _ck(self, rc):
+        return _check(rc, self._L)
+
     def close(self):
         if getattr(self, "_h", None):
-            lib().mp3d_batch_destroy(self._h)
+            self._L.mp3d_batch_destroy(self._h)
             self._h = None
 
     __del__ = close
 
     def reset(self):
-        _check(lib().mp3d_batch_reset(self._h))
+        self._ck(self._L.mp3d_batch_reset(self._h))
 
     def set_options(self, flags):
         """MP3D_OPT_* flags (OPT_CRC_CHECK) for later decode calls."""
-        _check(lib().mp3d_batch_set_options(self._h, int(flags)))
+        self._ck(self._L.mp3d_batch_set_options(self._h, int(flags)))
 
     def sync(self):
-        _check(lib().mp3d_batch_sync(self._h))
+        self._ck(self._L.mp3d_batch_sync(self._h))
 
     def set_timing(self, on=True):
-        _check(lib().mp3d_batch_set_timing(self._h, int(on)))
+        self._ck(self._L.mp3d_batch_set_timing(self._h, int(on)))
 
     def kernel_times_us(self):
         t = np.zeros(3, np.float32)
-        _check(lib().mp3d_batch_kernel_times(self._h, t.ctypes.data))
+        self._ck(self._L.mp3d_batch_kernel_times(self._h, t.ctypes.data))
         return dict(zip(("demux", "huffman", "synth"), t.tolist()))
 
     @staticmethod
@@ -281,15 +321,15 @@ class BatchDecoder:
         fp, k1 = _ptr(frames)
         pp, k2 = _ptr(pcm)
         ip, k3 = _ptr(infos)
-        fn = lib().mp3d_batch_decode_f32 if f32 else lib().mp3d_batch_decode
-        _check(fn(self._h, fp, off.ctypes.data, sz.ctypes.data, n, F, pp, ip, ctypes.c_void_p(stream) if stream else None))
+        fn = self._L.mp3d_batch_decode_f32 if f32 else self._L.mp3d_batch_decode
+        self._ck(fn(self._h, fp, off.ctypes.data, sz.ctypes.data, n, F, pp, ip, ctypes.c_void_p(stream) if stream else None))
         return pcm, infos
 
     def set_output(self, hz, channels):
         """Format of the packed sink (decode_packed): hz from RATES, channels
         1 or 2; hz = 0 turns the sink off and frees its buffers.  A change
         restarts every stream's resampler."""
-        _check(lib().mp3d_batch_set_output(self._h, int(hz), int(channels)))
+        self._ck(self._L.mp3d_batch_set_output(self._h, int(hz), int(channels)))
         self._out = (int(hz), int(channels))
 
     def decode_packed(self, frames, offsets, sizes, frames_per_stream, out=None, counts=None, infos=None, f32=True,
@@ -318,7 +358,7 @@ class BatchDecoder:
         op, k2 = _ptr(out)
         cp, k3 = _ptr(counts)
         ip, k4 = _ptr(infos)
-        _check(lib().mp3d_batch_decode_packed(self._h, fp, off.ctypes.data, sz.ctypes.data, n, F, op, int(bool(f32)),
+        self._ck(self._L.mp3d_batch_decode_packed(self._h, fp, off.ctypes.data, sz.ctypes.data, n, F, op, int(bool(f32)),
                                               stride, cp, PACK_FLUSH if flush else 0, ip,
                                               ctypes.c_void_p(stream) if stream else None))
         return out, counts, infos
@@ -327,7 +367,7 @@ class BatchDecoder:
         """Device-side microseconds of the resample stage of the last packed
         call (after set_timing)."""
         t = ctypes.c_float()
-        _check(lib().mp3d_batch_resample_time(self._h, ctypes.byref(t)))
+        self._ck(self._L.mp3d_batch_resample_time(self._h, ctypes.byref(t)))
         return float(t.value)
 
     @staticmethod
@@ -358,7 +398,7 @@ class BatchDecoder:
         if self._nbytes(out) != n * state_bytes():
             raise ValueError("out holds %d bytes, %d streams need %d" % (self._nbytes(out), n, n * state_bytes()))
         op, k = _ptr(out)
-        _check(lib().mp3d_batch_get_state(self._h, first, n, op))
+        self._ck(self._L.mp3d_batch_get_state(self._h, first, n, op))
         return out
 
     def set_state(self, buf, first=0):
@@ -374,12 +414,12 @@ class BatchDecoder:
             raise ValueError("state buffer of %d bytes is not a whole number of %d-byte blobs" % (nb, state_bytes()))
         first, n = self._state_range(first, nb // state_bytes())
         bp, k = _ptr(buf)
-        _check(lib().mp3d_batch_set_state(self._h, first, n, bp))
+        self._ck(self._L.mp3d_batch_set_state(self._h, first, n, bp))
 
     def stream_info(self, n_streams):
         """[StreamInfo] of the first n_streams streams (after a decode call)."""
         arr = (StreamInfo * int(n_streams))()
-        _check(lib().mp3d_batch_stream_info(self._h, int(n_streams), ctypes.cast(arr, ctypes.c_void_p)))
+        self._ck(self._L.mp3d_batch_stream_info(self._h, int(n_streams), ctypes.cast(arr, ctypes.c_void_p)))
         return list(arr)
 
     def decode_long(self, data, segment_frames=32, max_frames=None, pcm=None, infos=None, f32=False):
@@ -409,7 +449,7 @@ class BatchDecoder:
         ip, k3 = _ptr(infos)
         n = ctypes.c_longlong()
         si = StreamInfo()
-        _check(lib().mp3d_batch_decode_long(self._h, dp, nbytes, int(segment_frames), pp, int(f32), int(max_frames),
+        self._ck(self._L.mp3d_batch_decode_long(self._h, dp, nbytes, int(segment_frames), pp, int(f32), int(max_frames),
                                             ip, ctypes.byref(n), ctypes.byref(si)))
         return pcm[: n.value], infos[: n.value], si
 
@@ -419,7 +459,7 @@ class BatchDecoder:
         is_out = np.zeros((n, F, 2, 2, 576), np.int16)
         sf_out = np.zeros((n, F, 2, 2, 40), np.uint8)
         fp, k1 = _ptr(frames)
-        _check(lib().mp3d_batch_huffman_only(self._h, fp, off.ctypes.data, sz.ctypes.data, n, F,
+        self._ck(self._L.mp3d_batch_huffman_only(self._h, fp, off.ctypes.data, sz.ctypes.data, n, F,
                                              is_out.ctypes.data, sf_out.ctypes.data, None))
         return is_out, sf_out
 
@@ -432,7 +472,7 @@ class BatchDecoder:
         bp, k2 = _ptr(block_type)
         mp, k3 = _ptr(mixed)
         pp, k4 = _ptr(pcm)
-        _check(lib().mp3d_batch_synth_only(self._h, xp, bp, mp, n, F, int(nch), int(hz), pp,
+        self._ck(self._L.mp3d_batch_synth_only(self._h, xp, bp, mp, n, F, int(nch), int(hz), pp,
                                            ctypes.c_void_p(stream) if stream else None))
         return pcm
 

@@ -1,6 +1,9 @@
 """Build the native libraries in-tree (hipcc for gfx950; gcc for CPU tools).
 
   mp3_amd/libmp3d.so    HIP kernels + C ABI (the product)
+  mp3_amd/libmp3d_wglds.so  the same sources with -DMP3D_WG_LDS_POISON: every
+                        workgroup fills its static LDS with 0xFF at entry
+                        (a debug build for the tests; not shipped)
   mp3_amd/libmp3gen.so  synthetic stream generator (bench/test input)
   oracle/liboracle.so   CPU restatement (test infrastructure only)
 """
@@ -50,12 +53,25 @@ def compile_hip(src_dir, out, obj_dir, extra=()):
     return out
 
 
+def _hip_deps():
+    return [CSRC / n for n in HIP_SRCS + HIP_HDRS] + [ROOT / "include" / "mp3d.h", pathlib.Path(__file__)]
+
+
 def build_hip(force=False):
     out = ROOT / "mp3_amd" / "libmp3d.so"
-    deps = [CSRC / n for n in HIP_SRCS + HIP_HDRS] + [ROOT / "include" / "mp3d.h", pathlib.Path(__file__)]
-    if force or _stale(out, deps):
+    if force or _stale(out, _hip_deps()):
         compile_hip(CSRC, out, ROOT / "mp3_amd" / "_obj")
     return out
+
+
+WGLDS_LIB = ROOT / "mp3_amd" / "libmp3d_wglds.so"
+
+
+def build_wglds(force=False):
+    """The per-workgroup LDS poison build (MP3D_LDS_ENTRY, mp3d_device.h)."""
+    if force or _stale(WGLDS_LIB, _hip_deps()):
+        compile_hip(CSRC, WGLDS_LIB, ROOT / "mp3_amd" / "_obj" / "wglds", extra=["-DMP3D_WG_LDS_POISON"])
+    return WGLDS_LIB
 
 
 def build_gen(force=False):
@@ -86,6 +102,7 @@ def build_examples(force=False):
 
 def build_all(force=False):
     build_hip(force)
+    build_wglds(force)
     build_gen(force)
     build_oracle(force)
     build_examples(force)

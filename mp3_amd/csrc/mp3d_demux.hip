@@ -24,6 +24,7 @@ k_demux(const uint8_t *__restrict__ in, const uint64_t *__restrict__ in_off, con
         FrameRec *__restrict__ rec, uint64_t *__restrict__ sideu, DevInfo *__restrict__ infos, int F, int opts) {
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4))); /* (an array of HIP's uint4 stays in scratch) */
     __shared__ __attribute__((aligned(16))) u32x4 s_stage[DMX_STAGE / 16];
+    MP3D_LDS_ENTRY();
     const int s = blockIdx.x, lane = threadIdx.x;
     const uint64_t base = in_off[s];
     const uint32_t len = in_len[s];
@@ -176,6 +177,7 @@ __global__ void __launch_bounds__(64) k_walk(const uint8_t *__restrict__ in, con
     /* frame words and sample rates in LDS: a constant-table read per frame
      * from L2 was a round trip on the frame chain */
     __shared__ uint32_t s_fw[9 * 16], s_hz[9];
+    MP3D_LDS_ENTRY();
     const int lane = threadIdx.x;
     for (int i = lane; i < 9 * 16; i += 64) s_fw[i] = (&c_frame_word[0][0])[i];
     if (lane < 9) s_hz[lane] = MP3D_SAMPLE_RATE[lane];
@@ -367,6 +369,7 @@ __global__ void __launch_bounds__(64 * MDC_WAVES) k_mdcopy(const uint8_t *__rest
                                                          const uint64_t *__restrict__ md_off,
                                                          StreamState *__restrict__ st,
                                                          const FrameRec *__restrict__ rec, int n_streams, int F) {
+    MP3D_LDS_ENTRY();
     const int lane = threadIdx.x & 63;
     /* wave-uniform (SGPR): the buffer resource below must not be per lane */
     const int s = blockIdx.x * MDC_WAVES + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -523,6 +526,7 @@ k_demux_fp(const uint8_t *__restrict__ in, uint32_t len, FpOffs fo, uint8_t *__r
     __shared__ DevInfo s_inf[FP_MAX];
     __shared__ int s_fin[3];
     __shared__ uint32_t s_tab[HDR_TAB_WORDS];
+    MP3D_LDS_ENTRY();
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane((int)(tid >> 6));
     constexpr int NT = 64 * FP_WAVES;

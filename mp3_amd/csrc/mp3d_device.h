@@ -39,4 +39,30 @@ __device__ __forceinline__ void wave_sync() { __asm__ volatile("" ::: "memory");
 
 __device__ __forceinline__ uint32_t bswap32(uint32_t x) { return __builtin_bswap32(x); }
 
+/* MP3D_LDS_ENTRY(): the first statement of every kernel (tests/
+ * test_wglds_coverage.py), nothing in the product build.  In the debug build
+ * libmp3d_wglds.so (-DMP3D_WG_LDS_POISON, mp3_amd/_build.py) every workgroup
+ * fills its whole static LDS allocation [0, group_segment_fixed_size) with
+ * 0xFF before anything else, then meets at a barrier: a read of LDS the
+ * workgroup itself did not write sees all-ones words (NaN as float) in EVERY
+ * workgroup, not what the previous workgroup on the CU left.  The launch-level
+ * k_lds_poison only reaches the first workgroup placed on a CU. */
+#ifdef MP3D_WG_LDS_POISON
+typedef volatile __attribute__((address_space(3))) uint32_t lds_vu32;
+typedef volatile __attribute__((address_space(3))) uint8_t lds_vu8;
+__device__ __forceinline__ void lds_entry_fill() {
+    const uint32_t bytes = __builtin_amdgcn_groupstaticsize();
+    const uint32_t nt = blockDim.x * blockDim.y * blockDim.z;
+    const uint32_t t = (threadIdx.z * blockDim.y + threadIdx.y) * blockDim.x + threadIdx.x;
+    /* static LDS starts at LDS address 0 (an integer made a pointer, not a
+     * null pointer constant: that one is ~0 in this address space) */
+    for (uint32_t i = t; i < bytes / 4u; i += nt) *(lds_vu32 *)(uintptr_t)(i * 4u) = 0xFFFFFFFFu;
+    for (uint32_t i = (bytes & ~3u) + t; i < bytes; i += nt) *(lds_vu8 *)(uintptr_t)i = 0xFFu;
+    __syncthreads();
+}
+#define MP3D_LDS_ENTRY() ::mp3d::lds_entry_fill()
+#else
+#define MP3D_LDS_ENTRY()
+#endif
+
 } // namespace mp3d

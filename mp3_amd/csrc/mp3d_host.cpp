@@ -2237,3 +2237,43 @@ extern "C" const char *mp3d_strerror(int e) {
 }
 extern "C" int mp3d_last_hip_error(void) { return g_last_hip; }
 extern "C" int mp3d_abi_version(void) { return MP3D_ABI_VERSION; }
+
+#ifdef MP3D_WG_LDS_POISON
+/* libmp3d_wglds.so only (the build whose every workgroup fills its static
+ * LDS at entry, MP3D_LDS_ENTRY): the positive control of that fill.  Leaves
+ * 0x5A5A5A5A in the CUs' LDS, then runs n_groups probe workgroups
+ * (k_wglds_probe) and copies what each found in its static LDS after the
+ * entry fill to out_words[g * words ...]; words >= the return value of a
+ * call with out_words = NULL (the probe's LDS size in words, rounded up).
+ * Returns the probe's static LDS size in bytes as the device reports it. */
+namespace mp3d {
+int wglds_probe_words();
+void launch_wglds_probe(int, int, uint32_t *, hipStream_t);
+} // namespace mp3d
+extern "C" __attribute__((visibility("default"))) int mp3d_debug_wglds_probe(int device, int n_groups,
+                                                                             uint32_t *out_words, int words) {
+    const int W = wglds_probe_words();
+    if (!out_words) return W;
+    if (n_groups <= 0 || n_groups > (1 << 16) || words < W) return MP3D_E_ARG;
+    int r = device_init(device);
+    if (r) return r;
+    uint32_t *d = nullptr;
+    const size_t n = (size_t)n_groups * (W + 1);
+    HIPCHK(hipMalloc(&d, n * sizeof(uint32_t)));
+    std::vector<uint32_t> h(n);
+    hipError_t e = hipMemset(d, 0, n * sizeof(uint32_t));
+    if (e == hipSuccess) {
+        launch_wglds_probe(g_dev[device].n_cu, n_groups, d, nullptr);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(h.data(), d, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    HIPCHK(e);
+    int bytes = (int)h[W];
+    for (int g = 0; g < n_groups; g++) {
+        memcpy(out_words + (size_t)g * words, &h[(size_t)g * (W + 1)], sizeof(uint32_t) * W);
+        if ((int)h[(size_t)g * (W + 1) + W] != bytes) bytes = -1; /* (every workgroup reports the same size) */
+    }
+    return bytes < 0 ? MP3D_E_HIP : bytes;
+}
+#endif

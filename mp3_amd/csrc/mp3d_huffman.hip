@@ -26,6 +26,7 @@ namespace mp3d {
 __global__ void __launch_bounds__(RANK_BLOCK) k_rank(const uint64_t *__restrict__ sideu, int n_units,
                                                      uint32_t *__restrict__ perm) {
     __shared__ uint32_t h[RANK_BINS];
+    MP3D_LDS_ENTRY();
     const int tid = threadIdx.x, seg0 = blockIdx.x * RANK_SEG;
     for (int i = tid; i < RANK_BINS; i += RANK_BLOCK) h[i] = 0u;
     __syncthreads();
@@ -83,6 +84,7 @@ __global__ void __launch_bounds__(HUFF_BLOCK) k_huffman(const uint8_t *__restric
      * code): signed bytes [q2, q0, q3, q1], so each 2 x int16 output word is
      * one v_perm_b32 (sign-extension selectors read odd bytes only) */
     __shared__ uint32_t s_c1s[256];
+    MP3D_LDS_ENTRY();
     huff_tables_lane(tab, s_lut, s_tsel, s_lbnd, s_slen);
     static_assert(HUFF_BLOCK >= 256, "s_c1s: one entry per thread");
     if (threadIdx.x < 256) {
@@ -415,6 +417,7 @@ __global__ void __launch_bounds__(64 * HW_UNITS) k_huffman_wave(const uint8_t *_
     __shared__ uint32_t s_tsel[32];
     __shared__ uint16_t s_lbnd[9][24];
     __shared__ uint8_t s_slen[32];
+    MP3D_LDS_ENTRY();
     huff_tables<64 * HW_UNITS>(tab, s_lut, s_tsel, s_lbnd, s_slen, threadIdx.x);
     __syncthreads();
     const int lane = threadIdx.x & 63;

@@ -47,6 +47,7 @@ __device__ __forceinline__ long long rs_emitted(long long n, const RsFilt &f) {
 __global__ void __launch_bounds__(MP3D_RS_THREADS)
 k_rs_plan(const DevInfo *__restrict__ inf, const RsState *__restrict__ st, const RsCfg *__restrict__ cfg, RsPlan *__restrict__ plan,
           int32_t *__restrict__ prefix, int32_t *__restrict__ out_count, int n, int F, long long stride, int flush) {
+    MP3D_LDS_ENTRY();
     const int s = blockIdx.x * MP3D_RS_THREADS + threadIdx.x;
     if (s >= n) return;
     int ri = st[s].rate_i;
@@ -143,6 +144,7 @@ k_rs_filter(const float *__restrict__ rows, const DevInfo *__restrict__ inf, con
             const RsCfg *__restrict__ cfg, const float *__restrict__ tab, const RsPlan *__restrict__ plan,
             const int32_t *__restrict__ prefix, void *__restrict__ out, int F, long long stride, int tiles) {
     __shared__ __attribute__((aligned(16))) float sx[(MP3D_RS_SPAN + 8) * OC];
+    MP3D_LDS_ENTRY();
     const int s = blockIdx.x / tiles, tile = blockIdx.x % tiles, t = threadIdx.x;
     const RsPlan P = plan[s];
     if (P.count <= 0) return;
@@ -262,6 +264,7 @@ __global__ void __launch_bounds__(MP3D_RS_THREADS)
 k_rs_update(const float *__restrict__ rows, const DevInfo *__restrict__ inf, RsState *__restrict__ st,
             const RsCfg *__restrict__ cfg, const RsPlan *__restrict__ plan, const int32_t *__restrict__ prefix, int F) {
     __shared__ float nh[MP3D_RS_HIST * OC];
+    MP3D_LDS_ENTRY();
     const int s = blockIdx.x, t = threadIdx.x;
     const RsPlan P = plan[s];
     RsState *S = st + s;

@@ -1545,6 +1545,7 @@ k_synth(const FrameRec *__restrict__ rec, const int16_t *__restrict__ is_buf, co
     /* two MPEG-1 workgroups per CU (4 waves per SIMD): <= half of the CU's 160 KB */
     static_assert(LSF || SRC_XR || sizeof(Lds) <= 160 * 1024 / 2, "k_synth: LDS for two workgroups per CU");
     __shared__ __attribute__((aligned(16))) Lds L;
+    MP3D_LDS_ENTRY();
     SynShared<LSF> &T = L.T;
     SynWave *Wv = L.Wv;
     auto &s_isq = L.isq;
@@ -1602,6 +1603,7 @@ k_synth(const FrameRec *__restrict__ rec, const int16_t *__restrict__ is_buf, co
 __global__ void __launch_bounds__(256) k_gather_frames(const uint4 *__restrict__ src, uint4 *__restrict__ dst,
                                                        const DevInfo *__restrict__ isrc, DevInfo *__restrict__ idst,
                                                        const int *__restrict__ a, int L, int F, int k0, int row16) {
+    MP3D_LDS_ENTRY();
     const int jl = blockIdx.x;           /* output frame relative to segment k0's first */
     const int k = jl / L;                /* segment relative to k0                      */
     const int j = (k0 + k) * L + jl % L; /* global output frame                         */
@@ -1647,7 +1649,6 @@ __global__ void __launch_bounds__(256) k_frame(const uint8_t *__restrict__ in_ho
         float pad_[64];
         SynWave w[2];
     } WvP;
-    SynWave *const Wv = WvP.w;
     __shared__ float s_xch[47 * 64]; /* granule 0 -> 1 hand-off: overlap (18), history (14 + 15) per lane */
     __shared__ __attribute__((aligned(16))) uint16_t s_lut[MP3D_LUT_MAX];
     __shared__ __attribute__((aligned(16))) uint32_t s_bits[HW_UNITS][HW_WORDS + 4];
@@ -1655,6 +1656,8 @@ __global__ void __launch_bounds__(256) k_frame(const uint8_t *__restrict__ in_ho
     __shared__ uint16_t s_lbnd[9][24];
     __shared__ uint8_t s_slen[32];
     __shared__ __attribute__((aligned(16))) uint32_t s_in[PF_BYTES / 4];
+    MP3D_LDS_ENTRY();
+    SynWave *const Wv = WvP.w;
     static_assert(PF_BYTES == 256 * 16 && MP3D_MAX_FRAME_BYTES <= 128 * 16, "k_frame: frame staging by wave 0");
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1818,18 +1821,76 @@ void launch_synth_xr(const float *xr, const uint8_t *bt, const uint8_t *mixed, c
  * workgroup the next kernel places on a CU finds all-ones words (NaN as
  * float) in any LDS it reads before writing, on every run -- not whatever
  * the previous kernel on that CU left.  160 KB per workgroup, so one per CU
- * at a time; 4 per CU. */
+ * at a time; 4 per CU.  Best effort: nothing places one of these workgroups
+ * on every CU, and only the FIRST workgroup of the next kernel on a CU sees
+ * the fill -- the later ones see what their predecessors left.  The
+ * guarantee for every workgroup is MP3D_LDS_ENTRY() (mp3d_device.h) in the
+ * debug build libmp3d_wglds.so; this kernel is the one without that fill. */
 #define LDS_POISON_WORDS (160 * 1024 / 4)
-__global__ void __launch_bounds__(1024) k_lds_poison() {
-    __shared__ uint32_t s[LDS_POISON_WORDS];
+__device__ __forceinline__ void lds_fill_all(uint32_t *s, uint32_t word) {
     /* volatile: LDS is dead at kernel end, so plain stores are removed */
     volatile uint32_t *v = s;
-    for (int i = threadIdx.x; i < LDS_POISON_WORDS; i += 1024) v[i] = 0xFFFFFFFFu;
+    for (int i = threadIdx.x; i < LDS_POISON_WORDS; i += 1024) v[i] = word;
+}
+
+__global__ void __launch_bounds__(1024) k_lds_poison() {
+    __shared__ uint32_t s[LDS_POISON_WORDS];
+    lds_fill_all(s, 0xFFFFFFFFu);
 }
 
 void launch_lds_poison(int n_cu, hipStream_t strm) {
     hipLaunchKernelGGL(k_lds_poison, dim3(4 * (n_cu > 0 ? n_cu : 256)), dim3(1024), 0, strm);
 }
+
+#ifdef MP3D_WG_LDS_POISON
+/* k_lds_poison with the fill word as an argument (the product's kernel keeps
+ * its code: the word is a constant there) */
+__global__ void __launch_bounds__(1024) k_lds_pattern(uint32_t word) {
+    __shared__ uint32_t s[LDS_POISON_WORDS];
+    MP3D_LDS_ENTRY();
+    lds_fill_all(s, word);
+}
+
+/* The debug build's positive control (mp3d_debug_wglds_probe, mp3d_host.cpp;
+ * tests/test_gpu_wglds.py): after a launch that left 0x5A5A5A5A in the LDS of
+ * the CUs, every one of n_groups small workgroups runs MP3D_LDS_ENTRY() and
+ * copies its whole static LDS allocation to out[group][WGLDS_PROBE_WORDS],
+ * bytes past the allocation's end as zeros, and the allocation's size in
+ * bytes to out[group][WGLDS_PROBE_WORDS].  The copy reads LDS through a
+ * volatile pointer from address 0, not through the object (a load of a
+ * __shared__ object nothing wrote may be folded); the object is written
+ * afterwards only so that the allocation exists.  4667 B: no multiple of 4,
+ * so the fill's byte tail runs; small, so several workgroups share a CU. */
+#define WGLDS_PROBE_WORDS 1167
+struct __attribute__((packed)) WgldsProbe {
+    uint32_t w[WGLDS_PROBE_WORDS - 1];
+    uint8_t b[3];
+};
+__global__ void __launch_bounds__(64) k_wglds_probe(uint32_t *__restrict__ out) {
+    __shared__ WgldsProbe s_probe;
+    MP3D_LDS_ENTRY();
+    uint32_t *o = out + (size_t)blockIdx.x * (WGLDS_PROBE_WORDS + 1);
+    const uint32_t bytes = min(__builtin_amdgcn_groupstaticsize(), 4u * WGLDS_PROBE_WORDS);
+    for (uint32_t i = threadIdx.x; i < bytes / 4u; i += 64u) o[i] = *(lds_vu32 *)(uintptr_t)(i * 4u);
+    if (threadIdx.x == 0) {
+        uint32_t tail = 0u;
+        for (uint32_t i = bytes & ~3u; i < bytes; i++) tail |= (uint32_t) * (lds_vu8 *)(uintptr_t)i << (8u * (i & 3u));
+        for (uint32_t i = bytes / 4u; i < WGLDS_PROBE_WORDS; i++) o[i] = i == bytes / 4u ? tail : 0u;
+        o[WGLDS_PROBE_WORDS] = __builtin_amdgcn_groupstaticsize();
+    }
+    __syncthreads();
+    volatile WgldsProbe *v = &s_probe;
+    for (uint32_t i = threadIdx.x; i < WGLDS_PROBE_WORDS - 1; i += 64u) v->w[i] = i;
+    if (threadIdx.x < 3) v->b[threadIdx.x] = (uint8_t)threadIdx.x;
+}
+
+int wglds_probe_words() { return WGLDS_PROBE_WORDS; }
+
+void launch_wglds_probe(int n_cu, int n_groups, uint32_t *out, hipStream_t strm) {
+    hipLaunchKernelGGL(k_lds_pattern, dim3(4 * (n_cu > 0 ? n_cu : 256)), dim3(1024), 0, strm, 0x5A5A5A5Au);
+    hipLaunchKernelGGL(k_wglds_probe, dim3(n_groups), dim3(64), 0, strm, out);
+}
+#endif
 
 void launch_gather_frames(const void *src, void *dst, const void *isrc, void *idst, const int *a, int L, int F, int k0,
                           int n_out, int bytes_per_row, hipStream_t strm) {

@@ -108,26 +108,35 @@ def reference(x, hz, out_hz):
     return y, (T + 2) * 2.0 ** -24 * S * A
 
 
-@pytest.fixture(scope="module")
-def plain(batch):
+def make_plain(batch):
     """Plain float32 rows and infos of the whole batch from a fresh handle."""
     dec = mp3_amd.BatchDecoder(batch.n, batch.F)
     offs, sizes = batch.geom()
     return dec.decode(batch.blob, offs, sizes, batch.F, f32=True)
 
 
-@pytest.fixture(scope="module")
-def expected(batch, plain):
-    """{(out_hz, out_ch): [(y float64, bound)] per stream}; computed once."""
+def make_expected(batch, plain, formats=FORMATS):
+    """{(out_hz, out_ch): [(y float64, bound)] per stream}."""
     rows, infos = plain
     out = {}
-    for hz_o, ch_o in FORMATS:
+    for hz_o, ch_o in formats:
         per = []
         for s in range(batch.n):
             hz, x = mapped_input(rows[s], infos[s], ch_o)
             per.append(reference(x, hz, hz_o) if hz else (np.zeros((0, ch_o)), 0.0))
         out[(hz_o, ch_o)] = per
     return out
+
+
+@pytest.fixture(scope="module")
+def plain(batch):
+    return make_plain(batch)
+
+
+@pytest.fixture(scope="module")
+def expected(batch, plain):
+    """Computed once."""
+    return make_expected(batch, plain)
 
 
 PATTERN = np.float32(-777.25)

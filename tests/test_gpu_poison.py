@@ -21,12 +21,26 @@ event) would read a run that is not there yet.  MP3D_DEBUG_RA_FAIL makes one
 next-run launch report an error after its kernels ran: the
 decoder must then refuse every call until a reset, never continue from the
 advanced state.
+
+Every test that exercises the kernels' LDS runs under two builds of the
+library (the `poison` fixture; the second run is the test's twin
+test_wglds_..., made at the end of the module): "product", as above, and
+"wglds", the debug build libmp3d_wglds.so in which EVERY workgroup of every kernel fills its
+whole static LDS with 0xFF at entry (MP3D_LDS_ENTRY, mp3d_device.h).  The
+launch-level k_lds_poison is best effort: it reaches at most the first
+workgroup the next kernel places on a CU, and the batch kernels run thousands
+of workgroups per launch; under "wglds" the later ones no longer see their
+predecessors' data either.  The helper-delay and failed-launch tests are about
+host ordering and run on the product build only.
 """
+import types
+
 import numpy as np
 import pytest
 
 import _golden
 import mp3_amd
+from mp3_amd import _build
 import test_gpu_golden_scale as GS
 import test_gpu_per_frame as PF
 import test_gpu_readahead as RA
@@ -36,9 +50,29 @@ import test_gpu_state_format as SF
 pytestmark = pytest.mark.gpu
 
 
+BUILDS = ["product", "wglds"]
+
+
 @pytest.fixture(autouse=True)
-def poison(monkeypatch):
+def poison(request, monkeypatch):
+    """The poison, under one of BUILDS.  A test as written below runs under
+    "product" and keeps the id it always had; the loop at the end of the module
+    gives every test that is not product_only a twin test_wglds_..., which
+    passes "wglds" to this fixture (indirect parametrisation)."""
+    build = getattr(request, "param", "product")
+    assert build in BUILDS, build
     monkeypatch.setenv("MP3D_DEBUG_POISON", "1")
+    if build == "wglds":
+        with mp3_amd.library(_build.WGLDS_LIB):
+            yield
+    else:
+        yield
+
+
+def product_only(f):
+    """A test about host ordering, not about the kernels' LDS: no wglds twin."""
+    f.product_only = True
+    return f
 
 
 @pytest.mark.parametrize("name", _golden.names())
@@ -88,6 +122,7 @@ def test_poison_long_and_host_sink():
     ST.test_host_sink_keeps_unwritten_bytes()
 
 
+@product_only
 @pytest.mark.parametrize("name", ["lsf_scale_24k_is", "bench_c5_g1", "keypress_128k_js", "c5_ms_is_mixed"])
 def test_helper_delay_readahead(monkeypatch, name):
     """The helper thread sleeps 3 ms before each next-run launch: the calls
@@ -101,6 +136,7 @@ def test_helper_delay_readahead(monkeypatch, name):
         RA._same(RA._run(RA._dec(ra), data, script), RA._run(RA._dec(0), data, script))
 
 
+@product_only
 def test_helper_delay_early_exits(monkeypatch):
     monkeypatch.setenv("MP3D_DEBUG_RA_DELAY_US", "3000")
     RA.test_readahead_early_exits()
@@ -112,6 +148,7 @@ def _stream():
     return data
 
 
+@product_only
 def test_failed_next_run_is_sticky(monkeypatch):
     """The first next-run launch fails after its kernels ran (so the device
     state is past the frames served): the decoder reports the error at the
@@ -141,6 +178,7 @@ def test_failed_next_run_is_sticky(monkeypatch):
     RA._same(RA._run(d, data, script), ref)
 
 
+@product_only
 def test_failed_next_run_then_set_state(monkeypatch):
     """After the sticky error, a state saved before the failure puts the
     decoder back (set_state clears the error): the stream then decodes from
@@ -229,3 +267,50 @@ def test_poison_gapless():
     GL.test_batch_gapless_matches_ffmpeg_tagged()
     GL.test_per_frame_gapless_matches_ffmpeg_tagged()
     GL.test_tag_split_across_calls()
+
+
+# ---- the packed sink (k_rs_plan, k_rs_filter, k_rs_update) under both builds
+import test_gpu_packed as PK  # noqa: E402
+
+
+@pytest.fixture(scope="module")
+def packed():
+    """test_gpu_packed's batch, its plain rows and the float64 reference:
+    once, from the product library without the poison (a module fixture is
+    set up before the first test's `poison`), shared and left unchanged."""
+    batch = PK.Batch()
+    plain = PK.make_plain(batch)
+    return batch, plain, PK.make_expected(batch, plain, [(48000, 2), (16000, 1)])
+
+
+@pytest.mark.parametrize("fmt", [(48000, 2), (16000, 1)])
+def test_poison_packed_values_and_counts(packed, fmt):
+    batch, _, expected = packed
+    PK.test_values_and_counts(batch, expected, fmt)
+
+
+def test_poison_packed_chunking(packed):
+    batch, plain, _ = packed
+    PK.test_chunking_is_bit_identical(batch, plain, (44100, 2))
+
+
+# ---- every test above once more under the wglds build: a twin function with
+# the same code, defaults and marks (so the same cases), named test_wglds_...,
+# whose `poison` fixture gets "wglds".  Opt out with @product_only, not in.
+def _twins():
+    made = {}
+    for name, f in list(globals().items()):
+        if not (name.startswith("test_") and isinstance(f, types.FunctionType) and f.__module__ == __name__):
+            continue
+        if getattr(f, "product_only", False):
+            continue
+        twin = types.FunctionType(f.__code__, f.__globals__, "test_wglds_" + name[len("test_"):], f.__defaults__,
+                                  f.__closure__)
+        twin.__doc__ = f.__doc__
+        twin.pytestmark = list(getattr(f, "pytestmark", [])) + [
+            pytest.mark.parametrize("poison", ["wglds"], indirect=True).mark]
+        made[twin.__name__] = twin
+    return made
+
+
+globals().update(_twins())

@@ -1,0 +1,156 @@
+"""Every kernel runs MP3D_LDS_ENTRY() before anything else (no GPU needed).
+
+The debug build libmp3d_wglds.so (mp3_amd/_build.py, -DMP3D_WG_LDS_POISON)
+poisons every workgroup's static LDS at kernel entry through that macro
+(mp3d_device.h; tests/test_gpu_wglds.py, tests/test_gpu_poison.py).  A kernel
+without it would silently escape that build, so: every __global__ definition
+in the four kernel sources except k_lds_poison (the launch-level fill, whose
+whole purpose is its own stores) has MP3D_LDS_ENTRY(); as the first statement
+after its __shared__ declarations -- only declarations that run no code may
+come before it -- and the macro is empty unless MP3D_WG_LDS_POISON is
+defined."""
+import re
+
+from mp3_amd import _build
+
+SOURCES = ["mp3d_demux.hip", "mp3d_huffman.hip", "mp3d_synth.hip", "mp3d_resample.hip"]
+EXPECTED = {"k_demux", "k_walk", "k_mdcopy", "k_demux_fp", "k_rank", "k_huffman", "k_huffman_wave", "k_synth",
+            "k_gather_frames", "k_frame", "k_rs_plan", "k_rs_filter", "k_rs_update"}
+MACRO = "MP3D_LDS_ENTRY()"
+# statements that may precede the macro: they declare, they run nothing
+DECL = ("typedef ", "constexpr ", "static_assert(", "struct ", "using ", "__shared__ ")
+
+
+def strip_comments(src):
+    src = re.sub(r"/\*.*?\*/", lambda m: re.sub(r"[^\n]", " ", m.group(0)), src, flags=re.S)
+    return re.sub(r"//[^\n]*", "", src)
+
+
+def _match(src, i, open_ch, close_ch):
+    """index just past the bracket that closes src[i] == open_ch"""
+    depth = 0
+    for j in range(i, len(src)):
+        if src[j] == open_ch:
+            depth += 1
+        elif src[j] == close_ch:
+            depth -= 1
+            if depth == 0:
+                return j + 1
+    raise ValueError("unbalanced %s" % open_ch)
+
+
+def statements(body):
+    """Top-level statements of a function body: text up to a ';' outside any
+    bracket, or up to the '}' of a loop's or branch's block (a type
+    definition or an initialiser in braces runs on to its ';')."""
+    out, depth, start = [], 0, 0
+    for j, c in enumerate(body):
+        if c in "({[":
+            depth += 1
+        elif c in ")}]":
+            depth -= 1
+            head = body[start:j].lstrip()
+            if c == "}" and depth == 0 and not re.match(r"(struct|union|enum|class|typedef|__shared__)\b|[^{(]*=", head):
+                out.append(body[start:j + 1])
+                start = j + 1
+        elif c == ";" and depth == 0:
+            out.append(body[start:j + 1])
+            start = j + 1
+    return [" ".join(s.split()) for s in out if s.strip()]
+
+
+def kernels(src):
+    """{name: [statements]} of every __global__ definition in src."""
+    src = strip_comments(src)
+    found = {}
+    for m in re.finditer(r"__global__", src):
+        paren = src.index("(", m.end())
+        while True:  # skip __launch_bounds__(...) / __attribute__((...)) up to the parameter list
+            name = re.search(r"(\w+)\s*$", src[m.end():paren]).group(1)
+            if name not in ("__launch_bounds__", "__attribute__"):
+                break
+            paren = src.index("(", _match(src, paren, "(", ")"))
+        after = _match(src, paren, "(", ")")
+        brace = re.match(r"\s*\{", src[after:])
+        assert brace, "%s: a __global__ declaration without a body" % name
+        start = after + brace.end() - 1
+        found[name] = statements(src[start + 1:_match(src, start, "{", "}") - 1])
+    return found
+
+
+def check(name, stmts):
+    assert MACRO + ";" in stmts, "%s: no %s;" % (name, MACRO)
+    k = stmts.index(MACRO + ";")
+    for s in stmts[:k]:
+        assert s.startswith(DECL), "%s: '%s' runs before %s" % (name, s[:60], MACRO)
+    for s in stmts[k + 1:]:
+        assert "__shared__" not in s, "%s: '%s' is declared after %s" % (name, s[:60], MACRO)
+    assert stmts.count(MACRO + ";") == 1, name
+
+
+def all_kernels():
+    found = {}
+    for f in SOURCES:
+        for name, stmts in kernels((_build.CSRC / f).read_text()).items():
+            assert name not in found, name
+            found[name] = stmts
+    return found
+
+
+def test_every_kernel_poisons_its_lds_at_entry():
+    found = all_kernels()
+    assert EXPECTED <= set(found), EXPECTED - set(found)
+    assert "k_lds_poison" in found and MACRO + ";" not in found.pop("k_lds_poison")
+    for name, stmts in found.items():
+        check(name, stmts)
+    assert sum("__shared__" in s for st in found.values() for s in st) >= 30  # (the parser sees the declarations)
+
+
+def test_the_check_catches_a_kernel_that_escapes():
+    """The parser and the rule on small sources of the shapes the kernels use."""
+    ok = """
+    template <bool A> /* c */
+    __global__ void __launch_bounds__((64 * Cfg<A>::W)) __attribute__((amdgpu_waves_per_eu(1, 8)))
+    k_a(const int *__restrict__ p, int n) {
+        constexpr int W = 4; // c
+        struct Lds { float a[4]; int b; };
+        __shared__ __attribute__((aligned(16))) Lds L;
+        __shared__ struct { float pad_[64]; } P;
+        MP3D_LDS_ENTRY();
+        if (n) return;
+        for (int i = 0; i < n; i++) { L.b = i; }
+    }
+    __global__ void k_b(int *p) {
+        MP3D_LDS_ENTRY();
+        p[0] = 1;
+    }"""
+    got = kernels(ok)
+    assert sorted(got) == ["k_a", "k_b"] and len(got["k_a"]) == 7 and len(got["k_b"]) == 2
+    for name, stmts in got.items():
+        check(name, stmts)
+    bad = {
+        "missing": "__global__ void k(int *p) { __shared__ int s[4]; p[0] = s[0]; }",
+        "after a return": "__global__ void k(int *p, int n) { if (n) return; MP3D_LDS_ENTRY(); p[0] = 1; }",
+        "after code": "__global__ void k(int *p) { __shared__ int s[4]; s[0] = 1; MP3D_LDS_ENTRY(); p[0] = s[0]; }",
+        "before a __shared__": "__global__ void k(int *p) { MP3D_LDS_ENTRY(); __shared__ int s[4]; p[0] = s[0]; }",
+        "in a branch": "__global__ void k(int *p, int n) { if (n) { MP3D_LDS_ENTRY(); } p[0] = 1; }",
+        "initialised declaration first": "__global__ void k(int *p) { const int t = p[0]; MP3D_LDS_ENTRY(); p[1] = t; }",
+    }
+    for what, src in bad.items():
+        (name, stmts), = kernels(src).items()
+        try:
+            check(name, stmts)
+        except AssertionError:
+            continue
+        raise AssertionError("not caught: " + what)
+
+
+def test_macro_is_empty_without_the_flag():
+    hdr = strip_comments((_build.CSRC / "mp3d_device.h").read_text())
+    m = re.search(r"#ifdef MP3D_WG_LDS_POISON\n(.*?)#else\n(.*?)#endif", hdr, re.S)
+    assert m, "mp3d_device.h: MP3D_LDS_ENTRY is defined under #ifdef MP3D_WG_LDS_POISON ... #else ... #endif"
+    on = re.findall(r"^#define MP3D_LDS_ENTRY\(\)(.*)$", m.group(1), re.M)
+    off = re.findall(r"^#define MP3D_LDS_ENTRY\(\)(.*)$", m.group(2), re.M)
+    assert len(on) == 1 and on[0].strip() and "__syncthreads()" in m.group(1)
+    assert len(off) == 1 and off[0].strip() == ""
+    assert len(re.findall(r"#define MP3D_LDS_ENTRY", hdr)) == 2
