@@ -292,9 +292,64 @@ MP3D_API int mp3d_batch_decode_packed(mp3d_batch *b, const uint8_t *frames, cons
                                       long long out_stride, int *out_count, int flags, mp3d_frame_info *infos,
                                       void *hip_stream);
 
-/* device-side microseconds of the resample stage of the last packed call
- * (needs mp3d_batch_set_timing) */
+/* device-side microseconds of the resample stage of the last packed call, or
+ * of the last chunk of the last mp3d_batch_decode_long_packed call (a stream
+ * of up to max_streams segments is one chunk); needs mp3d_batch_set_timing */
 MP3D_API int mp3d_batch_resample_time(mp3d_batch *b, float *us);
+
+/* ---- one long stream into the packed format (a player's open-file path) -- *
+ * Decodes a whole stream exactly as mp3d_batch_decode_long does (same L, same
+ * warm-up, max_frames >= L + 11, on scratch state) and writes it as ONE run
+ * of interleaved samples at out_hz and out_channels, gapless: the segments'
+ * rows are channel-mapped, trimmed and resampled on the GPU chunk by chunk,
+ * without an intermediate [n_frames][2304] buffer.
+ *
+ * Input signal x: the stream's frame slots in order; a slot with samples > 0
+ * contributes its samples per channel, a slot without audio (Xing/Info
+ * frame, dropped frame, garbage) nothing.  The input rate is fixed by the
+ * first audio frame, as in the packed sink; later frames that report another
+ * hz are fed at that rate.  *in_hz (may be NULL) gets it, 0 without audio.
+ * The channel map is the packed sink's, per frame, before the filter, in
+ * float32: mono -> stereo duplicates, stereo -> mono is 0.5f * (l + r).
+ *
+ * Trim: with MP3D_LONG_GAPLESS and a LAME / Lavf / Lavc extension in the
+ * stream's Xing/Info tag, x becomes x[skip_samples : stop], stop =
+ * min(end_sample, N) when end_sample >= 0, else N (mp3d_stream_info; FFmpeg
+ * semantics), in the input domain, before resampling.  Without the flag or
+ * such a tag x is untouched.  The resampler sees the trimmed signal starting
+ * at time 0 with zero history.
+ *
+ * Output: the packed sink's filter, flushed: exactly ceil(N' L / M) samples
+ * per channel for the N' inputs left after the trim,
+ *   y[m] = sum_j taps[p][j] x[n0 - (T/2 - 1) + j],  x outside [0, N') = 0,
+ * each accumulated by one float32 FMA chain in ascending j whatever block,
+ * tile or chunk computes it, so the samples are bit-identical to a flushed
+ * mp3d_batch_decode_packed of the same stream, for any L and max_streams.
+ * Equal rates are a copy.  f32 != 0: float32, else int16
+ * (clamp(floor(y * 32768 + 0.5))).  Samples are interleaved and contiguous
+ * from out.
+ *
+ * out is host or device memory of out_cap samples per channel; a device out
+ * must be aligned to one sample frame, else MP3D_E_ARG.  Nothing at or past
+ * out + out_cap * out_channels is touched, and nothing past the samples
+ * written.  *out_samples is always the full count; when it exceeds out_cap
+ * the first out_cap samples are written and valid and the call returns
+ * MP3D_E_CAPACITY.  sinfo (may be NULL) gets the stream info.
+ *
+ * Synchronous.  Needs no mp3d_batch_set_output and leaves the handle's
+ * output format, its resampler states, its per-stream decoder state and its
+ * options as they were.  MP3D_E_ARG: out_hz not one of the nine rates,
+ * out_channels not 1 or 2, NULL out_samples, L <= 0.                        */
+#define MP3D_LONG_GAPLESS 1
+MP3D_API int mp3d_batch_decode_long_packed(mp3d_batch *b, const uint8_t *data, size_t bytes, int L, int out_hz,
+                                           int out_channels, void *out, int f32, long long out_cap,
+                                           long long *out_samples, int flags, mp3d_stream_info *sinfo, int *in_hz);
+
+/* host only, no GPU: walks the frames as mp3d_long_plan does and returns
+ * ceil(n_slots * spf * L / M), spf (1152, LSF 576) and the input rate from
+ * the first slot's header: an upper bound of *out_samples for any flags.
+ * MP3D_E_ARG for a bad rate or a device pointer. */
+MP3D_API long long mp3d_long_packed_bound(const uint8_t *data, size_t bytes, int out_hz);
 
 /* ---- diagnostics -------------------------------------------------------- */
 MP3D_API const char *mp3d_strerror(int err);

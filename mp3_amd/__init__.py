@@ -53,9 +53,11 @@ EXPORTS = ["mp3d_dec_create", "mp3d_dec_create_on", "mp3d_dec_destroy", "mp3d_de
            "mp3d_long_plan", "mp3d_batch_set_options", "mp3d_dec_set_options", "mp3d_decode_frame_ex",
            "mp3d_state_bytes", "mp3d_batch_get_state", "mp3d_batch_set_state", "mp3d_dec_get_state",
            "mp3d_dec_set_state", "mp3d_resample_filter", "mp3d_batch_set_output", "mp3d_packed_max_samples",
-           "mp3d_batch_decode_packed", "mp3d_batch_resample_time"]
+           "mp3d_batch_decode_packed", "mp3d_batch_resample_time", "mp3d_batch_decode_long_packed",
+           "mp3d_long_packed_bound"]
 
 OPT_CRC_CHECK = 1  # MP3D_OPT_CRC_CHECK: drop frames whose CRC-16 mismatches
+LONG_GAPLESS = 1  # MP3D_LONG_GAPLESS: apply the LAME tag's trim inside decode_long_packed
 PACK_FLUSH = 1  # MP3D_PACK_FLUSH: feed zeros after the call's frames, then restart the resamplers
 RATES = (8000, 11025, 12000, 16000, 22050, 24000, 32000, 44100, 48000)
 FRAME_F32, FRAME_LAST = 1, 2  # mp3d_decode_frame_ex flags
@@ -113,6 +115,10 @@ def _bind(L):
     L.mp3d_packed_max_samples.restype = ctypes.c_longlong
     L.mp3d_batch_decode_packed.argtypes = [vp, vp, u64p, u32p, i, i, vp, i, ctypes.c_longlong, vp, i, vp, vp]
     L.mp3d_batch_resample_time.argtypes = [vp, vp]
+    L.mp3d_batch_decode_long_packed.argtypes = [vp, vp, ctypes.c_size_t, i, i, i, vp, i, ctypes.c_longlong,
+                                                ctypes.POINTER(ctypes.c_longlong), i, ctypes.POINTER(StreamInfo), ip]
+    L.mp3d_long_packed_bound.argtypes = [ctypes.c_char_p, ctypes.c_size_t, i]
+    L.mp3d_long_packed_bound.restype = ctypes.c_longlong
     if hasattr(L, "mp3d_debug_wglds_probe"):  # libmp3d_wglds.so only (tests/test_gpu_wglds.py)
         L.mp3d_debug_wglds_probe.argtypes = [i, i, vp, i]
     return L
@@ -453,6 +459,28 @@ class BatchDecoder:
                                             ip, ctypes.byref(n), ctypes.byref(si)))
         return pcm[: n.value], infos[: n.value], si
 
+    def decode_long_packed(self, data, out_hz, out_channels, segment_frames=32, out=None, f32=True, gapless=True):
+        """Frame-parallel decode of ONE long stream straight to interleaved
+        PCM at out_hz / out_channels (mp3d_batch_decode_long_packed): channel
+        map, gapless trim (gapless=True and a LAME tag) and resampling run on
+        the GPU.  data as in decode_long.  out: None (allocate a host array of
+        long_packed_bound samples) or a float32 (int16 with f32=False)
+        array/tensor [cap, out_channels], host or device.  Returns
+        (out[:n], StreamInfo, in_hz); raises MP3DError -5 when out is too
+        small (its first cap samples are valid then)."""
+        nbytes = data.numel() if hasattr(data, "numel") else len(data)
+        if out is None:
+            host = data.cpu().numpy().tobytes() if hasattr(data, "cpu") else bytes(data)
+            out = np.zeros((long_packed_bound(host, out_hz), int(out_channels)), np.float32 if f32 else np.int16)
+        dp, k1 = _ptr(data)
+        op, k2 = _ptr(out)
+        n, hz, si = ctypes.c_longlong(), ctypes.c_int(), StreamInfo()
+        self._ck(self._L.mp3d_batch_decode_long_packed(self._h, dp, nbytes, int(segment_frames), int(out_hz),
+                                                       int(out_channels), op, int(bool(f32)), len(out),
+                                                       ctypes.byref(n), LONG_GAPLESS if gapless else 0,
+                                                       ctypes.byref(si), ctypes.byref(hz)))
+        return out[: n.value], si, hz.value
+
     def huffman_only(self, frames, offsets, sizes, frames_per_stream):
         off, sz = self._geom(offsets, sizes)
         n, F = off.size, int(frames_per_stream)
@@ -497,6 +525,13 @@ def packed_max_samples(out_hz, frames, min_in_hz=8000):
     """Smallest stride of decode_packed that can never overflow for streams
     of input rate >= min_in_hz (mp3d_packed_max_samples)."""
     return int(_check(lib().mp3d_packed_max_samples(int(out_hz), int(frames), int(min_in_hz))))
+
+
+def long_packed_bound(data, out_hz):
+    """Upper bound of the samples per channel decode_long_packed writes for
+    this stream at out_hz (mp3d_long_packed_bound; host bytes, no GPU)."""
+    data = bytes(data)
+    return int(_check(lib().mp3d_long_packed_bound(data, len(data), int(out_hz))))
 
 
 def max_frame_slots(nbytes):

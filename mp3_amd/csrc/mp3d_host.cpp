@@ -50,6 +50,9 @@ void launch_frame(const uint8_t *, uint32_t, const uint64_t *, const uint32_t *,
                   bool, bool, uint32_t *, uint32_t, hipStream_t);
 void launch_resample(const float *, const void *, RsState *, const RsCfg *, int, const float *, RsPlan *, int32_t *,
                      void *, bool, int32_t *, int, int, long long, int, int, hipStream_t);
+void launch_resample_long(const float *, const void *, const int *, const uint32_t *, const RsCfg *, int, const float *,
+                          RsLong *, int32_t *, void *, bool, long long, int, int, int, int, int, int, int, int,
+                          hipStream_t);
 } // namespace mp3d
 
 using namespace mp3d;
@@ -407,6 +410,13 @@ struct mp3d_batch {
     size_t rs_rows_cap = 0, rs_prefix_cap = 0, rs_out_cap = 0;
     hipEvent_t ev_rs[2] = {};
     bool rs_timed = false; /* ev_rs hold a packed call's stage */
+    /* mp3d_batch_decode_long_packed to a rate other than rs_hz: the filters
+     * of its last output rate, kept for the next call (not the sink's) */
+    int lp_hz = 0;
+    RsCfg lp_cfg = {};
+    RsCfg *lp_dcfg = nullptr;
+    float *lp_tab = nullptr;
+    size_t lp_dcfg_cap = 0, lp_tab_cap = 0;
 };
 
 /* an event after all of the handle's work issued so far */
@@ -655,7 +665,8 @@ extern "C" void mp3d_batch_destroy(mp3d_batch *b) {
     if (b->copy) (void)hipStreamSynchronize(b->copy);
     void *ptrs[] = {b->st, b->rec, b->sideu, b->is_buf, b->meta, b->rank, b->geo[0].d, b->geo[1].d, b->d_work,
                     b->d_infos, b->md, b->d_in, b->d_pcm, b->d_xr, b->d_bt, b->d_mx, b->st_tail[0], b->st_tail[1],
-                    b->rs_dcfg, b->rs_st, b->rs_plan, b->rs_cnt, b->rs_tab, b->rs_rows, b->rs_prefix, b->rs_out};
+                    b->rs_dcfg, b->rs_st, b->rs_plan, b->rs_cnt, b->rs_tab, b->rs_rows, b->rs_prefix, b->rs_out,
+                    b->lp_dcfg, b->lp_tab};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     for (auto &g : b->geo) {
@@ -1125,91 +1136,99 @@ static int batch_decode(mp3d_batch *b, const uint8_t *frames, const uint64_t *of
                         int F, void *pcm, bool f32, mp3d_frame_info *infos, void *hip_stream, bool overwrite,
                         int kinds, bool mapped, int seg_len_req, const FpRun *fp, bool async);
 
-extern "C" int mp3d_batch_decode_long(mp3d_batch *b, const uint8_t *data, size_t bytes, int L, void *pcm, int f32,
-                                      long long max_frames, mp3d_frame_info *infos, long long *n_frames,
-                                      mp3d_stream_info *sinfo) {
-    if (!b || !data || !pcm || L <= 0 || max_frames <= 0 || !n_frames) return MP3D_E_ARG;
-    *n_frames = 0;
-    HIPCHK(hipSetDevice(b->device));
-    const bool dev_in = ptr_kind(data, b->device) != PTR_HOST; /* any GPU's: the walk needs a host copy */
-    std::vector<uint8_t> host_copy;
-    const uint8_t *hp = data;
-    if (dev_in) { /* the frame walk runs on the host */
-        host_copy.resize(bytes);
-        HIPCHK(hipMemcpy(host_copy.data(), data, bytes, hipMemcpyDefault));
-        hp = host_copy.data();
-    }
-    std::vector<uint64_t> off;
-    std::vector<long long> a;
-    int wmax = 0;
-    long long N = 0;
-    {
-        const int r = long_plan(hp, bytes, L, max_frames, off, a, &wmax);
-        if (r) return r;
-        N = (long long)off.size();
-    }
-    *n_frames = N;
-    if (N == 0) return MP3D_OK;
-    const long long K = (long long)a.size();
-    const int F = L + wmax;
-    if (F > b->max_frames) return MP3D_E_CAPACITY;
-    hipStream_t s = b->own;
-    {
-        int r = own_after_last(b);
-        if (!r) r = flush_tail(b, s); /* before b->st points at the scratch states */
-        if (r) return r;
-    }
-    const uint8_t *din = data;
-    if (!is_device_ptr(data, b->device)) { /* host or another GPU's: staged */
-        int r = grow(b, (void **)&b->d_in, &b->in_cap, bytes + 64);
-        if (r) return r;
-        HIPCHK(hipMemcpyAsync(b->d_in, data, bytes, hipMemcpyDefault, s));
-        din = b->d_in;
-    }
-    const size_t row = 2304 * (f32 ? sizeof(float) : sizeof(int16_t));
-    const bool pcm_dev = is_device_ptr(pcm, b->device), inf_dev = infos && is_device_ptr(infos, b->device);
-    const int chunk = b->max_streams;
-    void *seg_pcm = nullptr, *out_pcm = nullptr;
-    int *d_a = nullptr;
-    /* the virtual streams decode on a state array of their own: the handle's
-     * per-stream state (reservoir, overlap, FIFO, tag) is left as it was */
-    StreamState *const own_st = b->st, *seg_st = nullptr;
-    std::vector<int> a32;
-    mp3d_frame_info *out_inf = nullptr;
-    int rc = MP3D_OK;
+/* The segmented decode of one stream, shared by mp3d_batch_decode_long and
+ * mp3d_batch_decode_long_packed: plan() walks the frames, open() stages the
+ * input and allocates the scratch, decode_chunk(k0) decodes segments
+ * [k0, k0 + ns) as virtual streams into seg_pcm [ns][F][2304] (infos in
+ * b->d_infos), the destructor waits and gives the handle back as it was. */
 #define LCHK(x)                                                                                                        \
     do {                                                                                                               \
         hipError_t _e = (x);                                                                                           \
         if (_e != hipSuccess) {                                                                                        \
             g_last_hip = (int)_e;                                                                                      \
-            rc = MP3D_E_HIP;                                                                                           \
-            goto done;                                                                                                 \
+            return MP3D_E_HIP;                                                                                         \
         }                                                                                                              \
     } while (0)
-    LCHK(hipMalloc(&seg_pcm, (size_t)std::min<long long>(chunk, K) * F * row));
-    LCHK(hipMalloc(&seg_st, sizeof(StreamState) * (size_t)std::min<long long>(chunk, K)));
-    if (b->poison && (poison_dev(true, seg_pcm, (size_t)std::min<long long>(chunk, K) * F * row, s) ||
-                      poison_dev(true, seg_st, sizeof(StreamState) * (size_t)std::min<long long>(chunk, K), s))) {
-        rc = MP3D_E_HIP;
-        goto done;
+struct LongRun {
+    mp3d_batch *b;
+    /* the virtual streams decode on a state array of their own: the handle's
+     * per-stream state (reservoir, overlap, FIFO, tag) is left as it was */
+    StreamState *own_st;
+    hipStream_t s;
+    std::vector<uint8_t> host_copy;
+    std::vector<uint64_t> off;
+    std::vector<long long> a;
+    std::vector<int> a32;
+    const uint8_t *data = nullptr, *hp = nullptr, *din = nullptr;
+    size_t bytes = 0, row = 0;
+    long long N = 0, K = 0;
+    int L = 0, F = 0, chunk = 0;
+    bool f32 = false, swapped = false;
+    void *seg_pcm = nullptr;
+    StreamState *seg_st = nullptr;
+    int *d_a = nullptr;
+
+    explicit LongRun(mp3d_batch *b_) : b(b_), own_st(b_->st), s(b_->own) {}
+    ~LongRun() {
+        (void)hipStreamSynchronize(s);
+        b->st = own_st;
+        if (swapped) b->tail_live = -1; /* a tail left by the segments belongs to the scratch states */
+        if (seg_st) (void)hipFree(seg_st);
+        if (seg_pcm) (void)hipFree(seg_pcm);
+        if (d_a) (void)hipFree(d_a);
     }
-    b->st = seg_st;
-    LCHK(hipMalloc(&d_a, sizeof(int) * K));
-    a32.assign(a.begin(), a.end());
-    LCHK(hipMemcpyAsync(d_a, a32.data(), sizeof(int) * K, hipMemcpyHostToDevice, s));
-    out_pcm = pcm_dev ? pcm : nullptr;
-    if (!pcm_dev) LCHK(hipMalloc(&out_pcm, (size_t)N * row));
-    if (infos) {
-        out_inf = inf_dev ? infos : nullptr;
-        if (!inf_dev) LCHK(hipMalloc(&out_inf, sizeof(mp3d_frame_info) * (size_t)N));
+    /* the frame walk (on the host: a device stream is copied); N = 0: no frame */
+    int plan(const uint8_t *data_, size_t bytes_, int L_, long long max_frames) {
+        data = hp = data_;
+        bytes = bytes_;
+        L = L_;
+        if (ptr_kind(data, b->device) != PTR_HOST) { /* any GPU's: the walk needs a host copy */
+            host_copy.resize(bytes);
+            HIPCHK(hipMemcpy(host_copy.data(), data, bytes, hipMemcpyDefault));
+            hp = host_copy.data();
+        }
+        int wmax = 0;
+        const int r = long_plan(hp, bytes, L, max_frames, off, a, &wmax);
+        if (r) return r;
+        N = (long long)off.size();
+        K = (long long)a.size();
+        F = L + wmax;
+        return MP3D_OK;
     }
-    if (b->poison && ((!pcm_dev && poison_dev(true, out_pcm, (size_t)N * row, s)) ||
-                      (infos && !inf_dev && poison_dev(true, out_inf, sizeof(mp3d_frame_info) * (size_t)N, s)))) {
-        rc = MP3D_E_HIP;
-        goto done;
+    /* input staged, scratch allocated; chunk_ = segments per batch call */
+    int open(bool f32_, int chunk_) {
+        if (F > b->max_frames) return MP3D_E_CAPACITY;
+        f32 = f32_;
+        chunk = chunk_;
+        row = 2304 * (f32 ? sizeof(float) : sizeof(int16_t));
+        {
+            int r = own_after_last(b);
+            if (!r) r = flush_tail(b, s); /* before b->st points at the scratch states */
+            if (r) return r;
+        }
+        din = data;
+        if (!is_device_ptr(data, b->device)) { /* host or another GPU's: staged */
+            int r = grow(b, (void **)&b->d_in, &b->in_cap, bytes + 64);
+            if (r) return r;
+            HIPCHK(hipMemcpyAsync(b->d_in, data, bytes, hipMemcpyDefault, s));
+            din = b->d_in;
+        }
+        const size_t ns = (size_t)std::min<long long>(chunk, K);
+        LCHK(hipMalloc(&seg_pcm, ns * F * row));
+        LCHK(hipMalloc(&seg_st, sizeof(StreamState) * ns));
+        if (b->poison && (poison_dev(true, seg_pcm, ns * F * row, s) ||
+                          poison_dev(true, seg_st, sizeof(StreamState) * ns, s)))
+            return MP3D_E_HIP;
+        b->st = seg_st;
+        swapped = true;
+        LCHK(hipMalloc(&d_a, sizeof(int) * K));
+        a32.assign(a.begin(), a.end());
+        LCHK(hipMemcpyAsync(d_a, a32.data(), sizeof(int) * K, hipMemcpyHostToDevice, s));
+        return MP3D_OK;
     }
-    for (long long k0 = 0; k0 < K; k0 += chunk) {
-        const int ns = (int)std::min<long long>(chunk, K - k0);
+    int segments(long long k0) const { return (int)std::min<long long>(chunk, K - k0); }
+    int decode_chunk(long long k0) {
+        const int ns = segments(k0);
         std::vector<uint64_t> so(ns);
         std::vector<uint32_t> ss(ns);
         for (int i = 0; i < ns; i++) {
@@ -1220,26 +1239,62 @@ extern "C" int mp3d_batch_decode_long(mp3d_batch *b, const uint8_t *data, size_t
         /* fresh decoder state for every virtual stream */
         LCHK(state_clear(b->st, ns, s));
         b->tail_live = -1; /* fresh states: no tail of the previous chunk */
-        rc = batch_decode(b, din, so.data(), ss.data(), ns, F, seg_pcm, f32 != 0, nullptr, s, false);
-        if (rc) goto done;
-        if (k0 == 0 && sinfo) rc = mp3d_batch_stream_info(b, 1, sinfo);
-        if (rc) goto done;
-        const long long j0 = k0 * L, j1 = std::min(N, (k0 + ns) * L);
-        launch_gather_frames(seg_pcm, (uint8_t *)out_pcm + (size_t)j0 * row, b->d_infos, out_inf ? out_inf + j0 : nullptr,
-                             d_a + k0, L, F, (int)k0, (int)(j1 - j0), (int)row, s);
-        LCHK(hipGetLastError());
+        return batch_decode(b, din, so.data(), ss.data(), ns, F, seg_pcm, f32, nullptr, s, false);
     }
-    if (!pcm_dev) LCHK(hipMemcpyAsync(pcm, out_pcm, (size_t)N * row, hipMemcpyDefault, s));
-    if (infos && !inf_dev) LCHK(hipMemcpyAsync(infos, out_inf, sizeof(mp3d_frame_info) * (size_t)N, hipMemcpyDefault, s));
-    LCHK(hipStreamSynchronize(s));
-done:
-#undef LCHK
-    (void)hipStreamSynchronize(s);
-    b->st = own_st;
-    b->tail_live = -1; /* a tail left by the segments belongs to the scratch states */
-    if (seg_st) (void)hipFree(seg_st);
-    if (seg_pcm) (void)hipFree(seg_pcm);
-    if (d_a) (void)hipFree(d_a);
+};
+
+extern "C" int mp3d_batch_decode_long(mp3d_batch *b, const uint8_t *data, size_t bytes, int L, void *pcm, int f32,
+                                      long long max_frames, mp3d_frame_info *infos, long long *n_frames,
+                                      mp3d_stream_info *sinfo) {
+    if (!b || !data || !pcm || L <= 0 || max_frames <= 0 || !n_frames) return MP3D_E_ARG;
+    *n_frames = 0;
+    HIPCHK(hipSetDevice(b->device));
+    void *out_pcm = nullptr;
+    mp3d_frame_info *out_inf = nullptr;
+    const bool pcm_dev = is_device_ptr(pcm, b->device), inf_dev = infos && is_device_ptr(infos, b->device);
+    int rc;
+    {
+        LongRun R(b);
+        rc = R.plan(data, bytes, L, max_frames);
+        if (rc) return rc;
+        const long long N = R.N;
+        *n_frames = N;
+        if (N == 0) return MP3D_OK;
+        hipStream_t s = R.s;
+        /* the body in a lambda: every exit passes the frees below, after R's
+         * destructor has waited for the stream */
+        rc = [&]() -> int {
+            int r = R.open(f32 != 0, b->max_streams);
+            if (r) return r;
+            const size_t row = R.row;
+            out_pcm = pcm_dev ? pcm : nullptr;
+            if (!pcm_dev) LCHK(hipMalloc(&out_pcm, (size_t)N * row));
+            if (infos) {
+                out_inf = inf_dev ? infos : nullptr;
+                if (!inf_dev) LCHK(hipMalloc(&out_inf, sizeof(mp3d_frame_info) * (size_t)N));
+            }
+            if (b->poison && ((!pcm_dev && poison_dev(true, out_pcm, (size_t)N * row, s)) ||
+                              (infos && !inf_dev && poison_dev(true, out_inf, sizeof(mp3d_frame_info) * (size_t)N, s))))
+                return MP3D_E_HIP;
+            for (long long k0 = 0; k0 < R.K; k0 += R.chunk) {
+                const int ns = R.segments(k0);
+                r = R.decode_chunk(k0);
+                if (r) return r;
+                if (k0 == 0 && sinfo) r = mp3d_batch_stream_info(b, 1, sinfo);
+                if (r) return r;
+                const long long j0 = k0 * L, j1 = std::min(N, (k0 + ns) * L);
+                launch_gather_frames(R.seg_pcm, (uint8_t *)out_pcm + (size_t)j0 * row, b->d_infos,
+                                     out_inf ? out_inf + j0 : nullptr, R.d_a + k0, L, R.F, (int)k0, (int)(j1 - j0),
+                                     (int)row, s);
+                LCHK(hipGetLastError());
+            }
+            if (!pcm_dev) LCHK(hipMemcpyAsync(pcm, out_pcm, (size_t)N * row, hipMemcpyDefault, s));
+            if (infos && !inf_dev)
+                LCHK(hipMemcpyAsync(infos, out_inf, sizeof(mp3d_frame_info) * (size_t)N, hipMemcpyDefault, s));
+            LCHK(hipStreamSynchronize(s));
+            return MP3D_OK;
+        }();
+    }
     if (!pcm_dev && out_pcm) (void)hipFree(out_pcm);
     if (infos && !inf_dev && out_inf) (void)hipFree(out_inf);
     return rc;
@@ -2087,21 +2142,12 @@ static void rs_free(mp3d_batch *b) {
     b->rs_timed = false;
 }
 
-extern "C" int mp3d_batch_set_output(mp3d_batch *b, int out_hz, int out_channels) {
-    if (!b) return MP3D_E_ARG;
-    if (out_hz != 0 && (rs_rate_index(out_hz) < 0 || (out_channels != 1 && out_channels != 2))) return MP3D_E_ARG;
-    HIPCHK(hipSetDevice(b->device));
-    int r = own_after_last(b);
-    if (r) return r;
-    HIPCHK(hipStreamSynchronize(b->own));
-    if (out_hz == 0) {
-        rs_free(b);
-        return MP3D_OK;
-    }
-    /* one filter per input rate; rows padded to 4 floats for 16-byte loads */
-    RsCfg cfg = {};
+/* the filters of one output rate: one per input rate; rows padded to 4
+ * floats for 16-byte loads */
+static void rs_build(int out_hz, int out_channels, RsCfg &cfg, std::vector<float> &tab) {
+    cfg = RsCfg{};
     cfg.out_ch = out_channels;
-    std::vector<float> tab;
+    tab.clear();
     for (int i = 0; i < MP3D_RS_RATES; i++) {
         RsFilt &f = cfg.f[i];
         rs_sizes(RS_RATES[i], out_hz, &f.L, &f.M, &f.T);
@@ -2130,6 +2176,22 @@ extern "C" int mp3d_batch_set_output(mp3d_batch *b, int out_hz, int out_channels
         }
         f.tile = (int32_t)tile;
     }
+}
+
+extern "C" int mp3d_batch_set_output(mp3d_batch *b, int out_hz, int out_channels) {
+    if (!b) return MP3D_E_ARG;
+    if (out_hz != 0 && (rs_rate_index(out_hz) < 0 || (out_channels != 1 && out_channels != 2))) return MP3D_E_ARG;
+    HIPCHK(hipSetDevice(b->device));
+    int r = own_after_last(b);
+    if (r) return r;
+    HIPCHK(hipStreamSynchronize(b->own));
+    if (out_hz == 0) {
+        rs_free(b);
+        return MP3D_OK;
+    }
+    RsCfg cfg;
+    std::vector<float> tab;
+    rs_build(out_hz, out_channels, cfg, tab);
     const size_t ns = (size_t)b->max_streams;
     r = grow(b, (void **)&b->rs_dcfg, &b->rs_dcfg_cap, sizeof(RsCfg));
     if (!r) r = grow(b, (void **)&b->rs_st, &b->rs_st_cap, sizeof(RsState) * ns);
@@ -2221,6 +2283,134 @@ extern "C" int mp3d_batch_resample_time(mp3d_batch *b, float *us) {
     *us = ms * 1000.f;
     return MP3D_OK;
 }
+
+/* ------------------------------------------------------------------------ */
+/* One long stream into the packed sink's format      */
+/* ------------------------------------------------------------------------ */
+extern "C" long long mp3d_long_packed_bound(const uint8_t *data, size_t bytes, int out_hz) {
+    if (!data || rs_rate_index(out_hz) < 0 || ptr_kind(data, 0) != PTR_HOST) return MP3D_E_ARG;
+    std::vector<uint64_t> off;
+    std::vector<uint32_t> pay;
+    walk_frames(data, bytes, off, pay);
+    if (off.empty()) return 0;
+    const uint8_t *h = data + off[0];
+    const int ver = (h[1] >> 3) & 3, si = (h[2] >> 2) & 3;
+    const int hz = (int)MP3D_SAMPLE_RATE[si + (ver == 3 ? 0 : ver == 2 ? 3 : 6)];
+    int L, M, T;
+    rs_sizes(hz, out_hz, &L, &M, &T);
+    const long long n = (long long)off.size() * (host_frame_kind(h) == 1 ? 1152 : 576);
+    return (n * L + M - 1) / M;
+}
+
+extern "C" int mp3d_batch_decode_long_packed(mp3d_batch *b, const uint8_t *data, size_t bytes, int L, int out_hz,
+                                             int out_channels, void *out, int f32, long long out_cap,
+                                             long long *out_samples, int flags, mp3d_stream_info *sinfo, int *in_hz) {
+    if (!b || !data || !out_samples || L <= 0 || rs_rate_index(out_hz) < 0 || (out_channels != 1 && out_channels != 2) ||
+        out_cap < 0 || (!out && out_cap > 0) || (flags & ~MP3D_LONG_GAPLESS))
+        return MP3D_E_ARG;
+    *out_samples = 0;
+    if (in_hz) *in_hz = 0;
+    HIPCHK(hipSetDevice(b->device));
+    const int oc = out_channels;
+    const size_t eb = (f32 ? sizeof(float) : sizeof(int16_t)) * (size_t)oc; /* one sample frame */
+    const bool out_dev = is_device_ptr(out, b->device);
+    /* the kernel stores one sample frame per instruction, as the packed sink */
+    if (out_dev && (uintptr_t)out % eb) return MP3D_E_ARG;
+    /* a chunk's input count and its prefix are 32-bit */
+    const long long lim = 0x7fffffffLL / (1152LL * L);
+    if (lim < 1) return MP3D_E_CAPACITY;
+    RsLong *d_st = nullptr;
+    int32_t *d_prefix = nullptr;
+    void *d_out = nullptr;
+    int rc;
+    {
+        LongRun R(b);
+        rc = R.plan(data, bytes, L, 0x7fffffffffffffffLL);
+        if (rc) return rc;
+        if (R.N == 0) return MP3D_OK;
+        hipStream_t s = R.s;
+        rc = [&]() -> int {
+            int r = R.open(true, (int)std::min<long long>(b->max_streams, lim));
+            if (r) return r;
+            /* the filters: the sink's own when its rate matches, else those
+             * of the last call of this kind (the sink's stay as they are) */
+            const RsCfg *cfg = &b->rs_cfg, *dcfg = b->rs_dcfg;
+            const float *dtab = b->rs_tab;
+            if (b->rs_hz != out_hz) {
+                if (b->lp_hz != out_hz) {
+                    RsCfg c;
+                    std::vector<float> tab;
+                    rs_build(out_hz, 0, c, tab);
+                    b->lp_hz = 0;
+                    r = grow(b, (void **)&b->lp_dcfg, &b->lp_dcfg_cap, sizeof(RsCfg));
+                    if (!r) r = grow(b, (void **)&b->lp_tab, &b->lp_tab_cap, sizeof(float) * tab.size());
+                    if (r) return r;
+                    LCHK(hipMemcpyAsync(b->lp_dcfg, &c, sizeof(c), hipMemcpyHostToDevice, s));
+                    LCHK(hipMemcpyAsync(b->lp_tab, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice, s));
+                    LCHK(hipStreamSynchronize(s));
+                    b->lp_cfg = c;
+                    b->lp_hz = out_hz;
+                }
+                cfg = &b->lp_cfg;
+                dcfg = b->lp_dcfg;
+                dtab = b->lp_tab;
+            }
+            /* blocks per chunk: enough tiles for the most a chunk of any input
+             * rate can emit (its inputs plus a pending tail) */
+            const long long nf_max = std::min<long long>(R.N, (long long)R.chunk * L);
+            long long tiles = 1, whole = 0;
+            for (int i = 0; i < MP3D_RS_RATES; i++) {
+                const long long most = rs_bound(RS_RATES[i], out_hz, nf_max) + 1;
+                tiles = std::max(tiles, (most + cfg->f[i].tile - 1) / cfg->f[i].tile);
+                whole = std::max(whole, rs_bound(RS_RATES[i], out_hz, R.N));
+            }
+            if (tiles > 0x7fffffffLL) return MP3D_E_CAPACITY;
+            const long long cap = out_dev ? out_cap : std::min(out_cap, whole);
+            LCHK(hipMalloc(&d_st, sizeof(RsLong)));
+            LCHK(hipMalloc(&d_prefix, sizeof(int32_t) * (size_t)(nf_max + 1)));
+            if (!out_dev && cap > 0) LCHK(hipMalloc(&d_out, eb * (size_t)cap)); /* the device image of a host out */
+            if (b->poison && (poison_dev(true, d_st, sizeof(RsLong), s) ||
+                              poison_dev(true, d_prefix, sizeof(int32_t) * (size_t)(nf_max + 1), s) ||
+                              poison_dev(true, d_out, d_out ? eb * (size_t)cap : 0, s)))
+                return MP3D_E_HIP;
+            LCHK(hipMemsetAsync(d_st, 0, sizeof(RsLong), s)); /* the stream's start */
+            void *dout = out_dev ? out : d_out;
+            for (long long k0 = 0; k0 < R.K; k0 += R.chunk) {
+                const int ns = R.segments(k0);
+                r = R.decode_chunk(k0);
+                if (r) return r;
+                if (k0 == 0 && sinfo) r = mp3d_batch_stream_info(b, 1, sinfo);
+                if (r) return r;
+                const long long j0 = k0 * L, j1 = std::min(R.N, (k0 + ns) * L);
+                if (b->timing) LCHK(hipEventRecord(b->ev_rs[0], s));
+                if (b->poison) launch_lds_poison(g_dev[b->device].n_cu, s);
+                /* (the tag words of virtual stream 0 are read by the first
+                 * chunk's plan, before the next chunk clears the states) */
+                launch_resample_long((const float *)R.seg_pcm, b->d_infos, R.d_a + k0, &R.seg_st[0].tag_info, dcfg, oc, dtab,
+                                     d_st, d_prefix, dout, f32 != 0, cap, L, R.F, (int)k0, (int)(j1 - j0), (int)tiles,
+                                     k0 == 0, k0 + ns >= R.K, (flags & MP3D_LONG_GAPLESS) ? 1 : 0, s);
+                if (b->timing) { /* mp3d_batch_resample_time: the last chunk's stage */
+                    LCHK(hipEventRecord(b->ev_rs[1], s));
+                    b->rs_timed = true;
+                }
+                LCHK(hipGetLastError());
+            }
+            RsLong end;
+            LCHK(hipMemcpyAsync(&end, d_st, offsetof(RsLong, hist), hipMemcpyDeviceToHost, s));
+            LCHK(hipStreamSynchronize(s));
+            *out_samples = end.m1;
+            if (in_hz) *in_hz = end.rate_i ? RS_RATES[end.rate_i - 1] : 0;
+            const long long wrote = std::min<long long>(end.m1, cap);
+            if (!out_dev && wrote > 0) LCHK(hipMemcpy(out, d_out, eb * (size_t)wrote, hipMemcpyDefault));
+            return end.m1 > out_cap ? MP3D_E_CAPACITY : MP3D_OK;
+        }();
+    }
+    if (d_st) (void)hipFree(d_st);
+    if (d_prefix) (void)hipFree(d_prefix);
+    if (d_out) (void)hipFree(d_out);
+    return rc;
+}
+#undef LCHK
 
 /* ------------------------------------------------------------------------ */
 extern "C" const char *mp3d_strerror(int e) {

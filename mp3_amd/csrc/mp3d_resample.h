@@ -61,4 +61,29 @@ struct RsPlan {
 
 /* prefix[s * (F + 1) + f]: input samples of the call before frame f */
 
+/*
+ * The long-stream sink (mp3d_batch_decode_long_packed): ONE stream, decoded
+ * in chunks of virtual streams; after each chunk's decode three kernels run
+ * on the chunk's segment rows [ns][F][2304] in place (no gathered rows):
+ *   k_rsl_plan    one block : prefix sum of the chunk's output frames' input
+ *                             samples (block scan per stride), rate, trim
+ *                             window, the chunk's outputs [m0, m1)
+ *   k_rsl_filter  block / output tile of the chunk : as k_rs_filter, input
+ *                             found through the prefix in the segments' rows
+ *   k_rsl_carry   one block : the last T - 1 inputs and the counts
+ * All positions are 64-bit and absolute: r counts the stream's inputs before
+ * the trim, q = r - lo those after it (the resampler's time axis), m outputs.
+ */
+struct RsLong {
+    int64_t raw;     /* inputs before the trim seen by earlier chunks          */
+    int64_t lo, hi;  /* trim window: inputs r in [lo, hi) are kept             */
+    int64_t q0, q1;  /* plan: trimmed inputs before / through this chunk       */
+    int64_t m0, m1;  /* plan: outputs [m0, m1) of this chunk; m1 carries over  */
+    int32_t rate_i;  /* 1 + input rate index, 0: no audio yet                  */
+    int32_t n_in;    /* plan: the chunk's inputs before the trim               */
+    float hist[MP3D_RS_HIST * 2]; /* inputs q0 - (T - 1) .. q0 - 1, as RsState  */
+};
+/* All zero = the stream's start.  lprefix[jl], jl <= n_out: the chunk's
+ * inputs (before the trim) before its output frame jl, in gather order. */
+
 #endif

@@ -23,6 +23,10 @@
  *    come from the table (at most 87 KB per rate pair, L2 / L1 resident) in
  *    16-byte loads of its phase's row, 4 FMAs per channel for each.
  *  - Equal rates: the staged samples are copied.
+ * These inner loops are rs_tile, shared with the long-stream sink below
+ * (k_rsl_plan / k_rsl_filter / k_rsl_carry, mp3d_batch_decode_long_packed):
+ * one stream, staged chunk by chunk straight from the segments' rows, with
+ * the gapless trim applied while staging.
  */
 #include "mp3d_device.h"
 #include "mp3d_resample.h"
@@ -138,6 +142,87 @@ __device__ __forceinline__ void rs_store(void *__restrict__ out, size_t at, cons
     }
 }
 
+/* The n outputs of one tile from its staged input span, by the whole block
+ * (thread t): output i of the tile is output M0 + i of the stream and goes to
+ * element at0 + i * OC of out; sx[0] is input X0 of the stream (M0 and X0 may
+ * both be reduced by the same multiples of L and M: k_rs_filter's are). */
+template <int OC, bool F32>
+__device__ __forceinline__ void rs_tile(const float *__restrict__ sx, const RsFilt &f, const float *__restrict__ tab,
+                                        long long M0, int n, long long X0, void *__restrict__ out, size_t at0, int t) {
+    if (f.T == 1) { /* equal rates: copy */
+        for (int mo = t; mo < n; mo += MP3D_RS_THREADS) {
+            const int xi = (int)(M0 + mo - X0);
+            float acc[OC];
+#pragma unroll
+            for (int c = 0; c < OC; c++) acc[c] = sx[xi * OC + c];
+            rs_store<OC, F32>(out, at0 + (size_t)mo * OC, acc);
+        }
+        return;
+    }
+    const float *ft = tab + f.off;
+    if (f.T == MP3D_RS_UP_TAPS) {
+        /* one phase per thread and pass: f.S is a multiple of L */
+        const int step = (int)((long long)f.S * f.M / f.L);
+        for (int r = t; r < f.S; r += MP3D_RS_THREADS) {
+            if (r >= n) break;
+            const long long mm = (M0 + r) * f.M;
+            const int p = (int)(mm % f.L);
+            int xi = (int)(mm / f.L - f.pre - X0);
+            float4 tp[MP3D_RS_UP_TAPS / 4];
+#pragma unroll
+            for (int j = 0; j < MP3D_RS_UP_TAPS / 4; j++) tp[j] = *(const float4 *)(ft + (size_t)p * f.Tp + 4 * j);
+            for (int mo = r; mo < n; mo += f.S, xi += step) {
+                float acc[OC];
+#pragma unroll
+                for (int c = 0; c < OC; c++) acc[c] = 0.0f;
+                const float *x = sx + xi * OC;
+#pragma unroll
+                for (int j = 0; j < MP3D_RS_UP_TAPS / 4; j++) {
+                    const float w[4] = {tp[j].x, tp[j].y, tp[j].z, tp[j].w};
+#pragma unroll
+                    for (int q = 0; q < 4; q++)
+#pragma unroll
+                        for (int c = 0; c < OC; c++) acc[c] = fmaf(w[q], x[(4 * j + q) * OC + c], acc[c]);
+                }
+                rs_store<OC, F32>(out, at0 + (size_t)mo * OC, acc);
+            }
+        }
+        return;
+    }
+    /* general: consecutive outputs on consecutive threads, taps from the table */
+    if (t >= n) return;
+    const long long mm = (M0 + t) * f.M;
+    int p = (int)(mm % f.L);
+    int xi = (int)(mm / f.L - f.pre - X0);
+    const int dq = (int)((long long)MP3D_RS_THREADS * f.M / f.L), dr = (int)((long long)MP3D_RS_THREADS * f.M % f.L);
+    const int T4 = f.T & ~3;
+    for (int mo = t; mo < n; mo += MP3D_RS_THREADS) {
+        float acc[OC];
+#pragma unroll
+        for (int c = 0; c < OC; c++) acc[c] = 0.0f;
+        const float *x = sx + xi * OC;
+        const float *w = ft + (size_t)p * f.Tp;
+        for (int j = 0; j < T4; j += 4) {
+            const float4 w4 = *(const float4 *)(w + j);
+            const float wq[4] = {w4.x, w4.y, w4.z, w4.w};
+#pragma unroll
+            for (int q = 0; q < 4; q++)
+#pragma unroll
+                for (int c = 0; c < OC; c++) acc[c] = fmaf(wq[q], x[(j + q) * OC + c], acc[c]);
+        }
+        for (int j = T4; j < f.T; j++)
+#pragma unroll
+            for (int c = 0; c < OC; c++) acc[c] = fmaf(w[j], x[j * OC + c], acc[c]);
+        rs_store<OC, F32>(out, at0 + (size_t)mo * OC, acc);
+        xi += dq;
+        p += dr;
+        if (p >= f.L) {
+            p -= f.L;
+            xi++;
+        }
+    }
+}
+
 template <int OC, bool F32>
 __global__ void __launch_bounds__(MP3D_RS_THREADS)
 k_rs_filter(const float *__restrict__ rows, const DevInfo *__restrict__ inf, const RsState *__restrict__ st,
@@ -183,79 +268,8 @@ k_rs_filter(const float *__restrict__ rows, const DevInfo *__restrict__ inf, con
         }
     }
     __syncthreads();
-    const size_t obase = (size_t)s * (size_t)stride * OC;
-    if (f.T == 1) { /* equal rates: copy */
-        for (int mo = (int)mA + t; mo < mB; mo += MP3D_RS_THREADS) {
-            const int xi = (int)(P.m0 + mo - P.pos) - relA;
-            float acc[OC];
-#pragma unroll
-            for (int c = 0; c < OC; c++) acc[c] = sx[xi * OC + c];
-            rs_store<OC, F32>(out, obase + (size_t)mo * OC, acc);
-        }
-        return;
-    }
-    const float *ft = tab + f.off;
-    if (f.T == MP3D_RS_UP_TAPS) {
-        /* one phase per thread and pass: f.S is a multiple of L */
-        const int step = (int)((long long)f.S * f.M / f.L);
-        for (int r = t; r < f.S; r += MP3D_RS_THREADS) {
-            if (mA + r >= mB) break;
-            const long long mm = (P.m0 + mA + r) * f.M;
-            const int p = (int)(mm % f.L);
-            int xi = (int)(mm / f.L - f.pre - P.pos) - relA;
-            float4 tp[MP3D_RS_UP_TAPS / 4];
-#pragma unroll
-            for (int j = 0; j < MP3D_RS_UP_TAPS / 4; j++) tp[j] = *(const float4 *)(ft + (size_t)p * f.Tp + 4 * j);
-            for (int mo = (int)mA + r; mo < mB; mo += f.S, xi += step) {
-                float acc[OC];
-#pragma unroll
-                for (int c = 0; c < OC; c++) acc[c] = 0.0f;
-                const float *x = sx + xi * OC;
-#pragma unroll
-                for (int j = 0; j < MP3D_RS_UP_TAPS / 4; j++) {
-                    const float w[4] = {tp[j].x, tp[j].y, tp[j].z, tp[j].w};
-#pragma unroll
-                    for (int q = 0; q < 4; q++)
-#pragma unroll
-                        for (int c = 0; c < OC; c++) acc[c] = fmaf(w[q], x[(4 * j + q) * OC + c], acc[c]);
-                }
-                rs_store<OC, F32>(out, obase + (size_t)mo * OC, acc);
-            }
-        }
-        return;
-    }
-    /* general: consecutive outputs on consecutive threads, taps from the table */
-    if (mA + t >= mB) return;
-    const long long mm = (P.m0 + mA + t) * f.M;
-    int p = (int)(mm % f.L);
-    int xi = (int)(mm / f.L - f.pre - P.pos) - relA;
-    const int dq = (int)((long long)MP3D_RS_THREADS * f.M / f.L), dr = (int)((long long)MP3D_RS_THREADS * f.M % f.L);
-    const int T4 = f.T & ~3;
-    for (int mo = (int)mA + t; mo < mB; mo += MP3D_RS_THREADS) {
-        float acc[OC];
-#pragma unroll
-        for (int c = 0; c < OC; c++) acc[c] = 0.0f;
-        const float *x = sx + xi * OC;
-        const float *w = ft + (size_t)p * f.Tp;
-        for (int j = 0; j < T4; j += 4) {
-            const float4 w4 = *(const float4 *)(w + j);
-            const float wq[4] = {w4.x, w4.y, w4.z, w4.w};
-#pragma unroll
-            for (int q = 0; q < 4; q++)
-#pragma unroll
-                for (int c = 0; c < OC; c++) acc[c] = fmaf(wq[q], x[(j + q) * OC + c], acc[c]);
-        }
-        for (int j = T4; j < f.T; j++)
-#pragma unroll
-            for (int c = 0; c < OC; c++) acc[c] = fmaf(w[j], x[j * OC + c], acc[c]);
-        rs_store<OC, F32>(out, obase + (size_t)mo * OC, acc);
-        xi += dq;
-        p += dr;
-        if (p >= f.L) {
-            p -= f.L;
-            xi++;
-        }
-    }
+    rs_tile<OC, F32>(sx, f, tab, P.m0 + mA, mB - (int)mA, P.pos + relA, out,
+                     ((size_t)s * (size_t)stride + (size_t)mA) * OC, t);
 }
 
 /* the state after the call: the last pre + post inputs, the position */
@@ -302,6 +316,250 @@ k_rs_update(const float *__restrict__ rows, const DevInfo *__restrict__ inf, RsS
         S->rate_i = P.rate_i;
         S->pos = pos;
     }
+}
+
+/* ------------------------------------------------------------------------ */
+/* The long-stream sink (mp3d_resample.h RsLong)       */
+/* ------------------------------------------------------------------------ */
+/* slot in the chunk's batch output of its output frame jl: k_gather_frames'
+ * indirection (a = the segments' first decoded frame, from the chunk's first) */
+__device__ __forceinline__ size_t rsl_slot(const int *__restrict__ a, int L, int F, int k0, int jl) {
+    const int k = jl / L;
+    const int j = (k0 + k) * L + jl % L;
+    return (size_t)k * F + (size_t)(j - a[k]);
+}
+
+/* a frame slot that feeds the sink (k_rs_plan's rule) */
+__device__ __forceinline__ bool rsl_audio(const DevInfo &d) {
+    return d.samples > 0 && d.samples <= 1152 && (d.channels == 1 || d.channels == 2);
+}
+
+/* k_rsl_plan is one block and latency-bound (a[k], then the frame's info, per
+ * frame): 1 024 threads x 8 frames make a stride 8 192 frames, so a chunk of
+ * 1 024 segments of 32 frames takes four */
+#define MP3D_RSL_PLAN_THREADS 1024
+#define MP3D_RSL_PER 8 /* frames per thread and stride of k_rsl_plan's scan */
+
+/* trimmed inputs seen once r inputs were seen */
+__device__ __forceinline__ long long rsl_trimmed(long long r, long long lo, long long hi) {
+    return max(min(r, hi) - lo, 0LL);
+}
+
+__global__ void __launch_bounds__(MP3D_RSL_PLAN_THREADS)
+k_rsl_plan(const DevInfo *__restrict__ inf, const int *__restrict__ a, const uint32_t *__restrict__ tag,
+           const RsCfg *__restrict__ cfg, RsLong *__restrict__ S, int32_t *__restrict__ prefix, int L, int F, int k0,
+           int n_out, int first, int last, int gapless) {
+    __shared__ int32_t wsum[MP3D_RSL_PLAN_THREADS / 64];
+    __shared__ int32_t s_base, s_first;
+    MP3D_LDS_ENTRY();
+    const int t = threadIdx.x;
+    if (t == 0) {
+        s_base = 0;
+        s_first = n_out;
+    }
+    __syncthreads();
+    /* the input rate: the stream's first audio frame (in the first stride of
+     * the first chunk, unless the stream opens with that many empty slots) */
+    const int ri0 = S->rate_i;
+    int ri = ri0;
+    if (!ri) {
+        for (int j0 = 0; j0 < n_out; j0 += MP3D_RSL_PLAN_THREADS) {
+            const int jl = j0 + t;
+            bool hit = false;
+            if (jl < n_out) {
+                const DevInfo d = inf[rsl_slot(a, L, F, k0, jl)];
+                hit = rsl_audio(d) && rs_rate_index(d.hz) >= 0;
+            }
+            if (hit) atomicMin(&s_first, jl);
+            if (__syncthreads_or(hit)) break;
+        }
+        if (s_first < n_out) ri = rs_rate_index(inf[rsl_slot(a, L, F, k0, s_first)].hz) + 1;
+    }
+    const int from = ri0 ? 0 : s_first; /* frames before the rate is known feed nothing */
+    /* exclusive prefix sum: PER consecutive frames per thread, a wave scan of
+     * the threads' sums, the waves' totals through LDS, the running base */
+    for (int j0 = 0; j0 < n_out; j0 += MP3D_RSL_PLAN_THREADS * MP3D_RSL_PER) {
+        const int jb = j0 + t * MP3D_RSL_PER;
+        int v[MP3D_RSL_PER], sum = 0;
+#pragma unroll
+        for (int i = 0; i < MP3D_RSL_PER; i++) {
+            const int jl = jb + i;
+            v[i] = 0;
+            if (jl < n_out && jl >= from) {
+                const DevInfo d = inf[rsl_slot(a, L, F, k0, jl)];
+                if (rsl_audio(d)) v[i] = d.samples;
+            }
+            sum += v[i];
+        }
+        int inc = sum;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int u = __shfl_up(inc, o, 64);
+            if ((t & 63) >= o) inc += u;
+        }
+        if ((t & 63) == 63) wsum[t >> 6] = inc;
+        __syncthreads();
+        int before = s_base;
+        for (int w = 0; w < (t >> 6); w++) before += wsum[w];
+        int run = before + inc - sum;
+#pragma unroll
+        for (int i = 0; i < MP3D_RSL_PER; i++) {
+            if (jb + i < n_out) prefix[jb + i] = run;
+            run += v[i];
+        }
+        __syncthreads();
+        if (t == MP3D_RSL_PLAN_THREADS - 1) s_base = before + inc;
+        __syncthreads();
+    }
+    if (t != 0) return;
+    const int n_in = s_base;
+    prefix[n_out] = n_in;
+    long long lo = S->lo, hi = S->hi;
+    if (first) {
+        /* tag_to_info (mp3d_host.cpp): FFmpeg's skip and end of the LAME tag */
+        lo = 0;
+        hi = INT64_MAX;
+        const uint32_t tg = tag[0];
+        if (gapless && (tg & MP3D_TAG_LAME)) {
+            lo = (long long)((tg >> 12) & 0xFFFu) + 529;
+            const int frames = (tg & MP3D_TAG_FRAMES) ? (int)tag[1] : -1;
+            if (frames > 0) {
+                const long long end = (long long)frames * ((int)tag[2] == 2 ? 576 : 1152) + 529 - (long long)(tg & 0xFFFu);
+                if (end >= 0) hi = end;
+            }
+        }
+        S->lo = lo;
+        S->hi = hi;
+    }
+    const long long r0 = S->raw, m0 = S->m1;
+    const long long q0 = rsl_trimmed(r0, lo, hi), q1 = rsl_trimmed(r0 + n_in, lo, hi);
+    long long m1 = m0;
+    if (ri) {
+        const RsFilt f = cfg->f[ri - 1];
+        m1 = last ? rs_ceil_div(q1 * f.L, f.M) : rs_emitted(q1, f);
+    }
+    S->rate_i = ri;
+    S->n_in = n_in;
+    S->q0 = q0;
+    S->q1 = q1;
+    S->m0 = m0;
+    S->m1 = max(m1, m0);
+}
+
+template <int OC, bool F32>
+__global__ void __launch_bounds__(MP3D_RS_THREADS)
+k_rsl_filter(const float *__restrict__ rows, const DevInfo *__restrict__ inf, const int *__restrict__ a,
+             const RsCfg *__restrict__ cfg, const float *__restrict__ tab, const RsLong *__restrict__ S,
+             const int32_t *__restrict__ prefix, void *__restrict__ out, long long cap, int L, int F, int k0, int n_out) {
+    __shared__ __attribute__((aligned(16))) float sx[(MP3D_RS_SPAN + 8) * OC];
+    MP3D_LDS_ENTRY();
+    const int t = threadIdx.x;
+    const long long mEnd = min((long long)S->m1, cap); /* nothing at or past the caller's capacity is written */
+    if (!S->rate_i || S->m0 >= mEnd) return;
+    const RsFilt f = cfg->f[S->rate_i - 1];
+    const long long mA = S->m0 + (long long)blockIdx.x * f.tile;
+    if (mA >= mEnd) return;
+    const long long mB = min(mEnd, mA + f.tile); /* outputs [mA, mB) of the stream */
+    /* trimmed inputs [qA, qA + len) of the tile */
+    const long long qA = (mA * f.M) / f.L - f.pre;
+    const long long qB = ((mB - 1) * f.M) / f.L + f.post + 1;
+    const int len = (int)min(qB - qA, (long long)MP3D_RS_SPAN); /* <= SPAN by the choice of f.tile */
+    const int HL = f.pre + f.post;
+    const long long q0 = S->q0, q1 = S->q1;
+    /* the carry before the chunk's samples; zeros before the stream's first
+     * sample and, in the last chunk, after its last */
+    for (int i = t; i < len; i += MP3D_RS_THREADS) {
+        const long long q = qA + i;
+        if (q >= q0 && q < q1) continue;
+        const long long h = q - (q0 - HL);
+        const bool old = q >= 0 && q < q0 && h >= 0;
+#pragma unroll
+        for (int c = 0; c < OC; c++) sx[i * OC + c] = old ? S->hist[h * OC + c] : 0.0f;
+    }
+    const long long qlo = max(qA, q0), qhi = min(qA + len, q1);
+    if (qlo < qhi) {
+        /* q -> sample of the chunk, before the trim */
+        const long long shift = S->lo - S->raw;
+        const int lo = (int)(qlo + shift), hi = (int)(qhi + shift);
+        const int sx0 = (int)(qlo - qA) - lo;
+        for (int fr = rs_frame_of(prefix, n_out, lo); fr < n_out; fr++) {
+            const int pa = prefix[fr], pb = prefix[fr + 1];
+            if (pa >= hi) break;
+            if (pb <= pa) continue;
+            const size_t sf = rsl_slot(a, L, F, k0, fr);
+            const int ch = inf[sf].channels;
+            const float *row = rows + sf * 2304;
+            for (int k = max(pa, lo) + t; k < min(pb, hi); k += MP3D_RS_THREADS) {
+                float v[OC];
+                rs_load<OC>(row, ch, k - pa, v);
+#pragma unroll
+                for (int c = 0; c < OC; c++) sx[(k + sx0) * OC + c] = v[c];
+            }
+        }
+    }
+    __syncthreads();
+    rs_tile<OC, F32>(sx, f, tab, mA, (int)(mB - mA), qA, out, (size_t)mA * OC, t);
+}
+
+/* the carry after the chunk: the last T - 1 trimmed inputs (from the old
+ * carry where the chunk holds fewer), the input count */
+template <int OC>
+__global__ void __launch_bounds__(MP3D_RS_THREADS)
+k_rsl_carry(const float *__restrict__ rows, const DevInfo *__restrict__ inf, const int *__restrict__ a,
+            const RsCfg *__restrict__ cfg, RsLong *__restrict__ S, const int32_t *__restrict__ prefix, int L, int F,
+            int k0, int n_out) {
+    __shared__ float nh[MP3D_RS_HIST * OC];
+    MP3D_LDS_ENTRY();
+    const int t = threadIdx.x;
+    const long long q0 = S->q0, q1 = S->q1, r0 = S->raw;
+    const int n_in = S->n_in;
+    if (S->rate_i && q1 > q0) {
+        const RsFilt f = cfg->f[S->rate_i - 1];
+        const int HL = f.pre + f.post;
+        const long long shift = S->lo - r0;
+        for (int i = t; i < HL; i += MP3D_RS_THREADS) {
+            const long long q = q1 - HL + i;
+            float v[OC];
+#pragma unroll
+            for (int c = 0; c < OC; c++) v[c] = 0.0f;
+            if (q >= q0) {
+                const int rel = (int)(q + shift);
+                const int fr = rs_frame_of(prefix, n_out, rel);
+                const size_t sf = rsl_slot(a, L, F, k0, fr);
+                rs_load<OC>(rows + sf * 2304, inf[sf].channels, rel - prefix[fr], v);
+            } else if (q >= 0 && q - (q0 - HL) >= 0) {
+#pragma unroll
+                for (int c = 0; c < OC; c++) v[c] = S->hist[(q - (q0 - HL)) * OC + c];
+            }
+#pragma unroll
+            for (int c = 0; c < OC; c++) nh[i * OC + c] = v[c];
+        }
+        __syncthreads();
+        for (int i = t; i < HL * OC; i += MP3D_RS_THREADS) S->hist[i] = nh[i];
+    }
+    if (t == 0) S->raw = r0 + n_in;
+}
+
+void launch_resample_long(const float *rows, const void *infos, const int *a, const uint32_t *tag, const RsCfg *cfg,
+                          int out_ch, const float *tab, RsLong *st, int32_t *prefix, void *out, bool f32, long long cap,
+                          int L, int F, int k0, int n_out, int tiles, int first, int last, int gapless, hipStream_t strm) {
+    const DevInfo *inf = (const DevInfo *)infos;
+    const dim3 blk(MP3D_RS_THREADS);
+    hipLaunchKernelGGL(k_rsl_plan, dim3(1), dim3(MP3D_RSL_PLAN_THREADS), 0, strm, inf, a, tag, cfg, st, prefix, L, F, k0,
+                       n_out, first, last, gapless);
+#define RSL_FILTER(OC, F32)                                                                                            \
+    hipLaunchKernelGGL((k_rsl_filter<OC, F32>), dim3((unsigned)tiles), blk, 0, strm, rows, inf, a, cfg, tab, st, prefix, \
+                       out, cap, L, F, k0, n_out)
+    if (out_ch == 2) {
+        if (f32) RSL_FILTER(2, true);
+        else RSL_FILTER(2, false);
+        hipLaunchKernelGGL(k_rsl_carry<2>, dim3(1), blk, 0, strm, rows, inf, a, cfg, st, prefix, L, F, k0, n_out);
+    } else {
+        if (f32) RSL_FILTER(1, true);
+        else RSL_FILTER(1, false);
+        hipLaunchKernelGGL(k_rsl_carry<1>, dim3(1), blk, 0, strm, rows, inf, a, cfg, st, prefix, L, F, k0, n_out);
+    }
+#undef RSL_FILTER
 }
 
 void launch_resample(const float *rows, const void *infos, RsState *st, const RsCfg *cfg, int out_ch, const float *tab,
