@@ -351,6 +351,95 @@ MP3D_API int mp3d_batch_decode_long_packed(mp3d_batch *b, const uint8_t *data, s
  * MP3D_E_ARG for a bad rate or a device pointer. */
 MP3D_API long long mp3d_long_packed_bound(const uint8_t *data, size_t bytes, int out_hz);
 
+/* ---- log-mel feature sink (a recogniser's front end) --------------------- *
+ * Input signal of a stream: its packed-sink output at 16 000 Hz, 1 channel,
+ * float32: x[0 .. N) since the stream's last restart.
+ *
+ * Frame t is centred on sample 160 t and covers x[160 t - 200 .. 160 t + 200),
+ * with x outside [0, N) = 0 (25 ms frames every 10 ms).
+ *   w[n] = 0.5 - 0.5 cos(2 pi n / 400), n = 0 .. 399          (periodic Hann)
+ *   X[k] = sum_n w[n] x[160 t - 200 + n] exp(-2 pi i n k / 400), k = 0 .. 200
+ *   P[k] = Re^2 + Im^2
+ * Mel scale, Slaney form (linear up to 1 kHz, then logarithmic):
+ *   mel(f) = 3 f / 200 for f < 1000, else 15 + ln(f / 1000) 27 / ln 6.4;
+ *   hz(m) is its inverse
+ *   c_i = hz(i mel(8000) / (n_mels + 1)), i = 0 .. n_mels + 1;  f_k = 40 k
+ *   F[j][k] = max(0, min((f_k - c_j) / (c_j+1 - c_j),
+ *                        (c_j+2 - f_k) / (c_j+2 - c_j+1))) 2 / (c_j+2 - c_j)
+ * computed in double and rounded to float; 1 <= n_mels <= 128.
+ *   mel[t][j] = sum_k F[j][k] P[k]
+ * Output feat[s][t][j], float32, time-major: mel[t][j], or with
+ * MP3D_FEAT_LOG10 log10(max(mel[t][j], 1e-10)).  There is no per-clip
+ * normalisation: a clip maximum is the caller's.
+ *
+ * Emit rule: frame t is emitted once sample 160 t + 199 has been seen, so
+ * after N samples a stream has emitted E(N) = floor((N - 200) / 160) + 1
+ * frames for N >= 200, else 0.  MP3D_PACK_FLUSH also emits every frame with
+ * 160 t < N, with zeros past N: the lifetime total is exactly ceil(N / 160),
+ * and the stream's feature state restarts.
+ *
+ * A frame's values are the same bits whatever call, tile or position in a
+ * tile computes it: every frame runs one fixed sequence of float32
+ * operations (a 200-point complex FFT of the packed real frame, the
+ * real-input unpack, the power, and each filter's products accumulated by
+ * one FMA chain in ascending k).  Against the exact value, with
+ * A = sum_n |w[n] x[n]| over the frame and d = 408 * 2^-24 * A,
+ *   |mel - exact| <= (sum_k F[j][k]) (2 sqrt 2 A d + 2 d^2) + 8 * 2^-24 exact.
+ *
+ * The per-stream feature state (a sample count and a carry of at most 399
+ * samples) lives in the handle while features are set, not in the state
+ * blob.  It restarts where the resampler's does: at create, at
+ * mp3d_batch_reset, at mp3d_batch_set_state on its slot, at
+ * mp3d_batch_set_output (which also turns features off), at
+ * mp3d_batch_set_features, after its own flush and after an overflow.      */
+#define MP3D_FEAT_LOG10 1
+
+/* host only, no GPU: fb[n_mels][201] floats (NULL: size only); cap = floats
+ * fb can hold; returns n_mels * 201 or MP3D_E_ARG */
+MP3D_API long long mp3d_mel_filterbank(int n_mels, float *fb, size_t cap);
+
+/* host only: a feat_stride that can never overflow for one call of `frames`
+ * frames per stream of input rate >= min_in_hz: ceil((S + 200) / 160) + 1
+ * with S = mp3d_packed_max_samples(16000, frames, min_in_hz); 0 when S is 0 */
+MP3D_API long long mp3d_feat_max_frames(int frames, int min_in_hz);
+
+/* Needs the packed sink set to (16000, 1), else MP3D_E_ARG.  n_mels = 0 turns
+ * the feature sink off and frees its buffers; flags: MP3D_FEAT_LOG10.  Uploads
+ * the filterbank (per-filter bin ranges plus weights), restarts every
+ * stream's feature state and waits for the handle's work. */
+MP3D_API int mp3d_batch_set_features(mp3d_batch *b, int n_mels, int flags);
+
+/* Decodes exactly as mp3d_batch_decode_packed does (decoder and resampler
+ * state advance exactly so) into a handle-owned sample buffer of stride
+ * mp3d_packed_max_samples(16000, frames_per_stream, 0), then stream s writes
+ * feat_count[s] frames of n_mels floats at feat + s * feat_stride * n_mels;
+ * nothing past them is touched.  A stream that would exceed feat_stride gets
+ * feat_count[s] = -1, writes nothing and has its feature state restarted.
+ * feat, feat_count and infos (may be NULL) are host or device memory; the
+ * call is asynchronous when all of them are device memory, and a host feat is
+ * filled by one copy per stream, as the packed call's out is.  flags:
+ * MP3D_PACK_FLUSH flushes the resampler, then the features.  MP3D_E_ARG
+ * before mp3d_batch_set_features.                                           */
+MP3D_API int mp3d_batch_decode_features(mp3d_batch *b, const uint8_t *frames, const uint64_t *offsets,
+                                        const uint32_t *sizes, int n_streams, int frames_per_stream, float *feat,
+                                        long long feat_stride, int *feat_count, int flags, mp3d_frame_info *infos,
+                                        void *hip_stream);
+
+/* The parity tap of the feature stage: feeds counts[s] (clamped to
+ * [0, sample_stride]) float32 16 kHz mono samples from samples +
+ * s * sample_stride per stream through the same kernels and the same
+ * per-slot state; feat, feat_stride, feat_count and flags as above.  samples
+ * and counts are host or device memory (a host samples array is read whole).
+ * It also turns the device output of mp3d_batch_decode_long_packed (16 kHz
+ * mono) into features.  Leaves the decoder and resampler state untouched.   */
+MP3D_API int mp3d_batch_features(mp3d_batch *b, const float *samples, long long sample_stride, const int *counts,
+                                 int n_streams, float *feat, long long feat_stride, int *feat_count, int flags,
+                                 void *hip_stream);
+
+/* device-side microseconds of the feature stage of the last feature call;
+ * needs mp3d_batch_set_timing */
+MP3D_API int mp3d_batch_feature_time(mp3d_batch *b, float *us);
+
 /* ---- diagnostics -------------------------------------------------------- */
 MP3D_API const char *mp3d_strerror(int err);
 MP3D_API int mp3d_last_hip_error(void);

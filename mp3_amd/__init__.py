@@ -54,11 +54,14 @@ EXPORTS = ["mp3d_dec_create", "mp3d_dec_create_on", "mp3d_dec_destroy", "mp3d_de
            "mp3d_state_bytes", "mp3d_batch_get_state", "mp3d_batch_set_state", "mp3d_dec_get_state",
            "mp3d_dec_set_state", "mp3d_resample_filter", "mp3d_batch_set_output", "mp3d_packed_max_samples",
            "mp3d_batch_decode_packed", "mp3d_batch_resample_time", "mp3d_batch_decode_long_packed",
-           "mp3d_long_packed_bound"]
+           "mp3d_long_packed_bound", "mp3d_mel_filterbank", "mp3d_feat_max_frames", "mp3d_batch_set_features",
+           "mp3d_batch_decode_features", "mp3d_batch_features", "mp3d_batch_feature_time"]
 
 OPT_CRC_CHECK = 1  # MP3D_OPT_CRC_CHECK: drop frames whose CRC-16 mismatches
 LONG_GAPLESS = 1  # MP3D_LONG_GAPLESS: apply the LAME tag's trim inside decode_long_packed
 PACK_FLUSH = 1  # MP3D_PACK_FLUSH: feed zeros after the call's frames, then restart the resamplers
+FEAT_LOG10 = 1  # MP3D_FEAT_LOG10: log10(max(mel, 1e-10)) instead of the mel energies
+MP3D_FEAT_LOG10 = FEAT_LOG10
 RATES = (8000, 11025, 12000, 16000, 22050, 24000, 32000, 44100, 48000)
 FRAME_F32, FRAME_LAST = 1, 2  # mp3d_decode_frame_ex flags
 
@@ -119,6 +122,14 @@ def _bind(L):
                                                 ctypes.POINTER(ctypes.c_longlong), i, ctypes.POINTER(StreamInfo), ip]
     L.mp3d_long_packed_bound.argtypes = [ctypes.c_char_p, ctypes.c_size_t, i]
     L.mp3d_long_packed_bound.restype = ctypes.c_longlong
+    L.mp3d_mel_filterbank.argtypes = [i, vp, ctypes.c_size_t]
+    L.mp3d_mel_filterbank.restype = ctypes.c_longlong
+    L.mp3d_feat_max_frames.argtypes = [i, i]
+    L.mp3d_feat_max_frames.restype = ctypes.c_longlong
+    L.mp3d_batch_set_features.argtypes = [vp, i, i]
+    L.mp3d_batch_decode_features.argtypes = [vp, vp, u64p, u32p, i, i, vp, ctypes.c_longlong, vp, i, vp, vp]
+    L.mp3d_batch_features.argtypes = [vp, vp, ctypes.c_longlong, vp, i, vp, ctypes.c_longlong, vp, i, vp]
+    L.mp3d_batch_feature_time.argtypes = [vp, vp]
     if hasattr(L, "mp3d_debug_wglds_probe"):  # libmp3d_wglds.so only (tests/test_gpu_wglds.py)
         L.mp3d_debug_wglds_probe.argtypes = [i, i, vp, i]
     return L
@@ -337,6 +348,7 @@ class BatchDecoder:
         restarts every stream's resampler."""
         self._ck(self._L.mp3d_batch_set_output(self._h, int(hz), int(channels)))
         self._out = (int(hz), int(channels))
+        self._mels = 0  # a change of the output format turns the feature sink off
 
     def decode_packed(self, frames, offsets, sizes, frames_per_stream, out=None, counts=None, infos=None, f32=True,
                       flush=False, stride=None, stream=None):
@@ -374,6 +386,73 @@ class BatchDecoder:
         call (after set_timing)."""
         t = ctypes.c_float()
         self._ck(self._L.mp3d_batch_resample_time(self._h, ctypes.byref(t)))
+        return float(t.value)
+
+    def set_features(self, n_mels, log10=True):
+        """Turn the log-mel feature sink on (mp3d_batch_set_features): n_mels
+        Slaney filters (1 .. 128) over 25 ms Hann frames every 10 ms of the
+        16 kHz mono packed output, log10(max(mel, 1e-10)) or, with
+        log10=False, the mel energies.  Needs set_output(16000, 1).  n_mels = 0
+        turns it off.  Restarts every stream's feature state."""
+        self._ck(self._L.mp3d_batch_set_features(self._h, int(n_mels), FEAT_LOG10 if log10 else 0))
+        self._mels = int(n_mels)
+
+    def _feat_args(self, n, feat, counts, stride, default_stride):
+        nm = getattr(self, "_mels", 0)
+        if stride is None:  # (features off: the call fails with MP3D_E_ARG)
+            stride = int(feat.shape[1]) if feat is not None else default_stride() if nm else 1
+        stride = int(stride)
+        if feat is None:
+            feat = np.zeros((n, stride, max(nm, 1)), np.float32)
+        if counts is None:
+            counts = np.zeros(n, np.int32)
+        return feat, counts, stride
+
+    def decode_features(self, frames, offsets, sizes, frames_per_stream, feat=None, counts=None, infos=None,
+                        flush=False, stride=None, stream=None):
+        """Decode as decode_packed does and write every stream's log-mel
+        frames (mp3d_batch_decode_features).  feat: None (allocate host) or
+        float32 array/tensor [n, stride, n_mels]; counts: None or int32
+        array/tensor [n]; infos as in decode.  stride defaults to feat's, else
+        to feat_max_frames.  flush=True ends the streams: resampler and
+        feature tails are emitted and both restart.  Returns (feat, counts,
+        infos); stream s holds counts[s] frames (-1: over the stride)."""
+        off, sz = self._geom(offsets, sizes)
+        n, F = off.size, int(frames_per_stream)
+        feat, counts, stride = self._feat_args(n, feat, counts, stride, lambda: feat_max_frames(F))
+        if infos is None:
+            infos = np.zeros((n, F), FRAME_INFO_DT)
+        fp, k1 = _ptr(frames)
+        op, k2 = _ptr(feat)
+        cp, k3 = _ptr(counts)
+        ip, k4 = _ptr(infos)
+        self._ck(self._L.mp3d_batch_decode_features(self._h, fp, off.ctypes.data, sz.ctypes.data, n, F, op, stride, cp,
+                                                    PACK_FLUSH if flush else 0, ip,
+                                                    ctypes.c_void_p(stream) if stream else None))
+        return feat, counts, infos
+
+    def features(self, samples, counts, feat=None, feat_counts=None, flush=False, stride=None, stream=None):
+        """The feature stage alone (mp3d_batch_features): samples float32
+        [n, sample_stride] 16 kHz mono, counts int32 [n] samples per stream
+        (both host arrays or device tensors), through the same kernels and
+        per-stream state as decode_features.  Returns (feat, feat_counts)."""
+        n, ss = int(samples.shape[0]), int(samples.shape[1])
+        if not hasattr(counts, "data_ptr"):
+            counts = np.ascontiguousarray(counts, np.int32)
+        feat, feat_counts, stride = self._feat_args(n, feat, feat_counts, stride, lambda: (ss + 200 + 159) // 160 + 1)
+        sp, k1 = _ptr(samples)
+        cp, k2 = _ptr(counts)
+        op, k3 = _ptr(feat)
+        fc, k4 = _ptr(feat_counts)
+        self._ck(self._L.mp3d_batch_features(self._h, sp if ss else None, ss, cp, n, op, stride, fc,
+                                             PACK_FLUSH if flush else 0, ctypes.c_void_p(stream) if stream else None))
+        return feat, feat_counts
+
+    def feature_time_us(self):
+        """Device-side microseconds of the feature stage of the last feature
+        call (after set_timing)."""
+        t = ctypes.c_float()
+        self._ck(self._L.mp3d_batch_feature_time(self._h, ctypes.byref(t)))
         return float(t.value)
 
     @staticmethod
@@ -525,6 +604,21 @@ def packed_max_samples(out_hz, frames, min_in_hz=8000):
     """Smallest stride of decode_packed that can never overflow for streams
     of input rate >= min_in_hz (mp3d_packed_max_samples)."""
     return int(_check(lib().mp3d_packed_max_samples(int(out_hz), int(frames), int(min_in_hz))))
+
+
+def mel_filterbank(n_mels):
+    """The feature sink's Slaney mel filterbank (mp3d_mel_filterbank; no GPU
+    needed): float32 [n_mels, 201] over the bins f_k = 40 k Hz."""
+    n = _check(lib().mp3d_mel_filterbank(int(n_mels), None, 0))
+    fb = np.zeros(n, np.float32)
+    _check(lib().mp3d_mel_filterbank(int(n_mels), fb.ctypes.data, fb.size))
+    return fb.reshape(int(n_mels), 201)
+
+
+def feat_max_frames(frames, min_in_hz=8000):
+    """Smallest stride of decode_features that can never overflow for streams
+    of input rate >= min_in_hz (mp3d_feat_max_frames)."""
+    return int(_check(lib().mp3d_feat_max_frames(int(frames), int(min_in_hz))))
 
 
 def long_packed_bound(data, out_hz):

@@ -27,6 +27,7 @@
 #include "mp3d_consts.h"
 #include "mp3d_hostparse.h"
 #include "mp3d_resample.h"
+#include "mp3d_features.h"
 
 namespace mp3d {
 hipError_t upload_synth_constants(const float *, const float *, const float *, const float *);
@@ -53,6 +54,8 @@ void launch_resample(const float *, const void *, RsState *, const RsCfg *, int,
 void launch_resample_long(const float *, const void *, const int *, const uint32_t *, const RsCfg *, int, const float *,
                           RsLong *, int32_t *, void *, bool, long long, int, int, int, int, int, int, int, int,
                           hipStream_t);
+void launch_features(const float *, const int32_t *, FtState *, FtPlan *, const FtTab *, float *, int32_t *, int,
+                     long long, long long, int, int, hipStream_t);
 } // namespace mp3d
 
 using namespace mp3d;
@@ -417,6 +420,20 @@ struct mp3d_batch {
     RsCfg *lp_dcfg = nullptr;
     float *lp_tab = nullptr;
     size_t lp_dcfg_cap = 0, lp_tab_cap = 0;
+    /* log-mel feature sink (mp3d_batch_set_features; mp3d_features.h):
+     * ft_mels = 0 is off, and then none of these buffers exists.  ft_st,
+     * ft_plan, ft_cin (sample counts of a call) and ft_cnt hold max_streams
+     * entries; ft_smp (the samples of a call) and ft_out (staging for a host
+     * sink) grow with the calls. */
+    int ft_mels = 0;
+    FtTab *ft_tab = nullptr;
+    FtState *ft_st = nullptr;
+    FtPlan *ft_plan = nullptr;
+    int32_t *ft_cin = nullptr, *ft_cnt = nullptr;
+    float *ft_smp = nullptr, *ft_out = nullptr;
+    size_t ft_tab_cap = 0, ft_st_cap = 0, ft_plan_cap = 0, ft_cin_cap = 0, ft_cnt_cap = 0, ft_smp_cap = 0, ft_out_cap = 0;
+    hipEvent_t ev_ft[2] = {};
+    bool ft_timed = false; /* ev_ft hold a feature call's stage */
 };
 
 /* an event after all of the handle's work issued so far */
@@ -625,6 +642,7 @@ extern "C" int mp3d_batch_create(int device, int max_streams, int max_frames, mp
     }
     for (int i = 0; i < 4; i++) (void)hipEventCreate(&b->ev[i]);
     for (int i = 0; i < 2; i++) (void)hipEventCreate(&b->ev_rs[i]);
+    for (int i = 0; i < 2; i++) (void)hipEventCreate(&b->ev_ft[i]);
     b->poison = poison_env();
     if (b->poison) {
         const size_t fr = (size_t)max_streams * max_frames;
@@ -666,7 +684,7 @@ extern "C" void mp3d_batch_destroy(mp3d_batch *b) {
     void *ptrs[] = {b->st, b->rec, b->sideu, b->is_buf, b->meta, b->rank, b->geo[0].d, b->geo[1].d, b->d_work,
                     b->d_infos, b->md, b->d_in, b->d_pcm, b->d_xr, b->d_bt, b->d_mx, b->st_tail[0], b->st_tail[1],
                     b->rs_dcfg, b->rs_st, b->rs_plan, b->rs_cnt, b->rs_tab, b->rs_rows, b->rs_prefix, b->rs_out,
-                    b->lp_dcfg, b->lp_tab};
+                    b->lp_dcfg, b->lp_tab, b->ft_tab, b->ft_st, b->ft_plan, b->ft_cin, b->ft_cnt, b->ft_smp, b->ft_out};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     for (auto &g : b->geo) {
@@ -677,6 +695,8 @@ extern "C" void mp3d_batch_destroy(mp3d_batch *b) {
     for (hipEvent_t e : b->ev)
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : b->ev_rs)
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : b->ev_ft)
         if (e) (void)hipEventDestroy(e);
     if (b->ev_done) (void)hipEventDestroy(b->ev_done);
     if (b->own) (void)hipStreamDestroy(b->own);
@@ -692,6 +712,7 @@ extern "C" int mp3d_batch_reset(mp3d_batch *b) {
     b->tail_live = -1; /* the state is zeroed whole */
     HIPCHK(state_clear(b->st, b->max_streams, b->own));
     if (b->rs_st) HIPCHK(hipMemsetAsync(b->rs_st, 0, sizeof(RsState) * (size_t)b->max_streams, b->own));
+    if (b->ft_st) HIPCHK(hipMemsetAsync(b->ft_st, 0, sizeof(FtState) * (size_t)b->max_streams, b->own));
     HIPCHK(hipStreamSynchronize(b->own));
     return MP3D_OK;
 }
@@ -1995,6 +2016,7 @@ static int state_copy(mp3d_batch *b, int first, int n, void *dst, const void *sr
                           hipMemcpyDefault, s));
     /* a restored state is a discontinuity: the slots' resamplers restart */
     if (!out && b->rs_st) HIPCHK(hipMemsetAsync(b->rs_st + first, 0, sizeof(RsState) * (size_t)n, s));
+    if (!out && b->ft_st) HIPCHK(hipMemsetAsync(b->ft_st + first, 0, sizeof(FtState) * (size_t)n, s));
     HIPCHK(hipStreamSynchronize(s));
     return MP3D_OK;
 }
@@ -2144,6 +2166,8 @@ static void rs_free(mp3d_batch *b) {
 
 /* the filters of one output rate: one per input rate; rows padded to 4
  * floats for 16-byte loads */
+static void ft_free(mp3d_batch *b);
+
 static void rs_build(int out_hz, int out_channels, RsCfg &cfg, std::vector<float> &tab) {
     cfg = RsCfg{};
     cfg.out_ch = out_channels;
@@ -2185,6 +2209,7 @@ extern "C" int mp3d_batch_set_output(mp3d_batch *b, int out_hz, int out_channels
     int r = own_after_last(b);
     if (r) return r;
     HIPCHK(hipStreamSynchronize(b->own));
+    ft_free(b); /* the feature sink reads this sink's format: off with any change of it */
     if (out_hz == 0) {
         rs_free(b);
         return MP3D_OK;
@@ -2280,6 +2305,232 @@ extern "C" int mp3d_batch_resample_time(mp3d_batch *b, float *us) {
     HIPCHK(hipEventSynchronize(b->ev_rs[1]));
     float ms = 0;
     HIPCHK(hipEventElapsedTime(&ms, b->ev_rs[0], b->ev_rs[1]));
+    *us = ms * 1000.f;
+    return MP3D_OK;
+}
+
+/* ------------------------------------------------------------------------ */
+/* Log-mel feature sink (mp3d_features.h)              */
+/* ------------------------------------------------------------------------ */
+static double ft_mel(double f) { return f < 1000.0 ? 3.0 * f / 200.0 : 15.0 + log(f / 1000.0) * 27.0 / log(6.4); }
+static double ft_hz(double m) { return m < 15.0 ? 200.0 * m / 3.0 : 1000.0 * exp((m - 15.0) * log(6.4) / 27.0); }
+
+/* the Slaney filterbank of include/mp3d.h, fb[n_mels][201] */
+static void ft_filterbank(int n_mels, float *fb) {
+    std::vector<double> c((size_t)n_mels + 2);
+    const double top = ft_mel(8000.0);
+    for (int i = 0; i < n_mels + 2; i++) c[i] = ft_hz(i * top / (n_mels + 1));
+    for (int j = 0; j < n_mels; j++)
+        for (int k = 0; k < MP3D_FT_BINS; k++) {
+            const double f = 40.0 * k;
+            const double up = (f - c[j]) / (c[j + 1] - c[j]), down = (c[j + 2] - f) / (c[j + 2] - c[j + 1]);
+            fb[(size_t)j * MP3D_FT_BINS + k] = (float)(std::max(0.0, std::min(up, down)) * 2.0 / (c[j + 2] - c[j]));
+        }
+}
+
+extern "C" long long mp3d_mel_filterbank(int n_mels, float *fb, size_t cap) {
+    if (n_mels < 1 || n_mels > MP3D_FT_MAX_MELS) return MP3D_E_ARG;
+    const long long n = (long long)n_mels * MP3D_FT_BINS;
+    if (fb) {
+        if ((long long)cap < n) return MP3D_E_ARG;
+        ft_filterbank(n_mels, fb);
+    }
+    return n;
+}
+
+/* the most frames S new samples can emit on top of a pending carry */
+static long long ft_bound(long long S) { return (S + MP3D_FT_HALF + MP3D_FT_HOP - 1) / MP3D_FT_HOP + 1; }
+
+extern "C" long long mp3d_feat_max_frames(int frames, int min_in_hz) {
+    const long long S = mp3d_packed_max_samples(16000, frames, min_in_hz);
+    if (S <= 0) return S;
+    return ft_bound(S);
+}
+
+static void ft_free(mp3d_batch *b) {
+    void **ptrs[] = {(void **)&b->ft_tab, (void **)&b->ft_st,  (void **)&b->ft_plan, (void **)&b->ft_cin,
+                     (void **)&b->ft_cnt, (void **)&b->ft_smp, (void **)&b->ft_out};
+    for (void **p : ptrs) {
+        if (*p) (void)hipFree(*p);
+        *p = nullptr;
+    }
+    b->ft_tab_cap = b->ft_st_cap = b->ft_plan_cap = b->ft_cin_cap = b->ft_cnt_cap = b->ft_smp_cap = b->ft_out_cap = 0;
+    b->ft_mels = 0;
+    b->ft_timed = false;
+}
+
+/* the transform's tables and the filterbank as ranges plus weights */
+static int ft_build(int n_mels, int flags, FtTab &t) {
+    memset(&t, 0, sizeof(t));
+    for (int n = 0; n < MP3D_FT_WIN; n++) t.win[n] = (float)(0.5 - 0.5 * cos(2.0 * M_PI * n / MP3D_FT_WIN));
+    for (int m = 0; m < MP3D_FT_HALF; m++) {
+        t.w200[m][0] = (float)cos(2.0 * M_PI * m / MP3D_FT_HALF);
+        t.w200[m][1] = (float)-sin(2.0 * M_PI * m / MP3D_FT_HALF);
+    }
+    for (int k = 0; k < MP3D_FT_BINS; k++) {
+        t.w400[k][0] = (float)cos(2.0 * M_PI * k / MP3D_FT_WIN);
+        t.w400[k][1] = (float)-sin(2.0 * M_PI * k / MP3D_FT_WIN);
+    }
+    std::vector<float> fb((size_t)n_mels * MP3D_FT_BINS);
+    ft_filterbank(n_mels, fb.data());
+    int used = 0;
+    for (int j = 0; j < n_mels; j++) {
+        const float *row = fb.data() + (size_t)j * MP3D_FT_BINS;
+        int lo = MP3D_FT_BINS, hi = -1;
+        for (int k = 0; k < MP3D_FT_BINS; k++)
+            if (row[k] != 0.0f) {
+                lo = std::min(lo, k);
+                hi = k;
+            }
+        const int len = hi < 0 ? 0 : hi - lo + 1;
+        if (used + len > MP3D_FT_MAX_WTS) return MP3D_E_ARG;
+        t.first[j] = len ? lo : 0;
+        t.len[j] = len;
+        t.off[j] = used;
+        for (int i = 0; i < len; i++) t.wts[used + i] = row[lo + i];
+        used += len;
+    }
+    t.n_mels = n_mels;
+    t.log10 = (flags & MP3D_FEAT_LOG10) ? 1 : 0;
+    return MP3D_OK;
+}
+
+extern "C" int mp3d_batch_set_features(mp3d_batch *b, int n_mels, int flags) {
+    if (!b || n_mels < 0 || n_mels > MP3D_FT_MAX_MELS || (flags & ~MP3D_FEAT_LOG10)) return MP3D_E_ARG;
+    if (n_mels && (b->rs_hz != 16000 || b->rs_ch != 1)) return MP3D_E_ARG;
+    HIPCHK(hipSetDevice(b->device));
+    int r = own_after_last(b);
+    if (r) return r;
+    HIPCHK(hipStreamSynchronize(b->own));
+    if (n_mels == 0) {
+        ft_free(b);
+        return MP3D_OK;
+    }
+    FtTab tab;
+    r = ft_build(n_mels, flags, tab);
+    if (r) return r;
+    const size_t ns = (size_t)b->max_streams;
+    r = grow(b, (void **)&b->ft_tab, &b->ft_tab_cap, sizeof(FtTab));
+    if (!r) r = grow(b, (void **)&b->ft_st, &b->ft_st_cap, sizeof(FtState) * ns);
+    if (!r) r = grow(b, (void **)&b->ft_plan, &b->ft_plan_cap, sizeof(FtPlan) * ns);
+    if (!r) r = grow(b, (void **)&b->ft_cin, &b->ft_cin_cap, sizeof(int32_t) * ns);
+    if (!r) r = grow(b, (void **)&b->ft_cnt, &b->ft_cnt_cap, sizeof(int32_t) * ns);
+    if (r) {
+        ft_free(b);
+        return r;
+    }
+    HIPCHK(hipMemcpyAsync(b->ft_tab, &tab, sizeof(tab), hipMemcpyHostToDevice, b->own));
+    /* a change of the features restarts every stream's feature state */
+    HIPCHK(hipMemsetAsync(b->ft_st, 0, sizeof(FtState) * ns, b->own));
+    HIPCHK(hipStreamSynchronize(b->own)); /* (tab is on this stack) */
+    b->ft_mels = n_mels;
+    b->ft_timed = false;
+    return MP3D_OK;
+}
+
+/* The feature stage on stream s: dsmp [n][sstride] samples and dcin [n]
+ * counts are device memory; feat and feat_count are the caller's (host or
+ * device).  Returns after the work is queued when both are device memory,
+ * else when it is done. */
+static int ft_run(mp3d_batch *b, const float *dsmp, const int32_t *dcin, long long sstride, int n, float *feat,
+                  long long feat_stride, int *feat_count, int flags, hipStream_t s) {
+    const int nm = b->ft_mels;
+    const bool out_dev = is_device_ptr(feat, b->device), cnt_dev = is_device_ptr(feat_count, b->device);
+    /* blocks per stream: enough tiles for the most frames the stride admits */
+    const long long stride = std::min(feat_stride, ft_bound(sstride));
+    const long long tiles = std::max<long long>(1, (stride + MP3D_FT_TILE - 1) / MP3D_FT_TILE);
+    if (tiles * n > 0x7fffffffLL) return MP3D_E_CAPACITY;
+    if (out_dev && (uintptr_t)feat % sizeof(float)) return MP3D_E_ARG;
+    int r = MP3D_OK;
+    if (!out_dev) r = grow(b, (void **)&b->ft_out, &b->ft_out_cap, sizeof(float) * nm * (size_t)stride * n + 16);
+    if (r) return r;
+    float *dout = out_dev ? feat : b->ft_out;
+    int32_t *dcnt = cnt_dev ? (int32_t *)feat_count : b->ft_cnt;
+    if (b->timing) HIPCHK(hipEventRecord(b->ev_ft[0], s));
+    if (b->poison) launch_lds_poison(g_dev[b->device].n_cu, s);
+    launch_features(dsmp, dcin, b->ft_st, b->ft_plan, b->ft_tab, dout, dcnt, n, sstride, out_dev ? feat_stride : stride,
+                    (int)tiles, (flags & MP3D_PACK_FLUSH) ? 1 : 0, s);
+    if (b->timing) {
+        HIPCHK(hipEventRecord(b->ev_ft[1], s));
+        b->ft_timed = true;
+    }
+    HIPCHK(hipGetLastError());
+    if (out_dev && cnt_dev) return MP3D_OK;
+    std::vector<int32_t> hc((size_t)n);
+    HIPCHK(hipMemcpyAsync(hc.data(), dcnt, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (!out_dev) {
+        /* only each stream's own frames reach the caller's buffer */
+        for (int i = 0; i < n; i++)
+            if (hc[i] > 0)
+                HIPCHK(hipMemcpyAsync(feat + (size_t)nm * (size_t)feat_stride * i, dout + (size_t)nm * (size_t)stride * i,
+                                      sizeof(float) * nm * (size_t)hc[i], hipMemcpyDefault, s));
+    }
+    if (!cnt_dev) HIPCHK(hipMemcpyAsync(feat_count, hc.data(), sizeof(int32_t) * n, hipMemcpyDefault, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return MP3D_OK;
+}
+
+extern "C" int mp3d_batch_decode_features(mp3d_batch *b, const uint8_t *frames, const uint64_t *offsets,
+                                          const uint32_t *sizes, int n, int F, float *feat, long long feat_stride,
+                                          int *feat_count, int flags, mp3d_frame_info *infos, void *hip_stream) {
+    if (!b || !b->ft_mels || !feat || !feat_count || feat_stride < 0 || (flags & ~MP3D_PACK_FLUSH)) return MP3D_E_ARG;
+    if (!frames || !offsets || !sizes || n <= 0 || F <= 0) return MP3D_E_ARG;
+    if (n > b->max_streams || F > b->max_frames) return MP3D_E_CAPACITY;
+    HIPCHK(hipSetDevice(b->device));
+    /* the packed call into the handle's own samples: a stride no stream can
+     * exceed, counts on the device, so it only queues work */
+    const long long S = mp3d_packed_max_samples(16000, F, 0);
+    int r = grow(b, (void **)&b->ft_smp, &b->ft_smp_cap, sizeof(float) * (size_t)S * n);
+    if (r) return r;
+    r = mp3d_batch_decode_packed(b, frames, offsets, sizes, n, F, b->ft_smp, 1, S, b->ft_cin, flags, infos, hip_stream);
+    if (r) return r;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : b->own;
+    CallEnd done{b, s};
+    return ft_run(b, b->ft_smp, b->ft_cin, S, n, feat, feat_stride, feat_count, flags, s);
+}
+
+extern "C" int mp3d_batch_features(mp3d_batch *b, const float *samples, long long sample_stride, const int *counts, int n,
+                                   float *feat, long long feat_stride, int *feat_count, int flags, void *hip_stream) {
+    if (!b || !b->ft_mels || !counts || !feat || !feat_count || sample_stride < 0 || feat_stride < 0 ||
+        (flags & ~MP3D_PACK_FLUSH))
+        return MP3D_E_ARG;
+    if ((!samples && sample_stride) || n <= 0) return MP3D_E_ARG;
+    if (n > b->max_streams) return MP3D_E_CAPACITY;
+    if (sample_stride > 0x7fffffffLL) return MP3D_E_ARG; /* counts are int */
+    HIPCHK(hipSetDevice(b->device));
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : b->own;
+    int r = call_begin(b, s);
+    if (r) return r;
+    CallEnd done{b, s};
+    const float *dsmp = samples;
+    const int32_t *dcin = (const int32_t *)counts;
+    bool host_in = false;
+    if (sample_stride && !is_device_ptr(samples, b->device)) {
+        r = grow(b, (void **)&b->ft_smp, &b->ft_smp_cap, sizeof(float) * (size_t)sample_stride * n);
+        if (r) return r;
+        HIPCHK(hipMemcpyAsync(b->ft_smp, samples, sizeof(float) * (size_t)sample_stride * n, hipMemcpyDefault, s));
+        dsmp = b->ft_smp;
+        host_in = true;
+    } else if (sample_stride && (uintptr_t)samples % sizeof(float)) {
+        return MP3D_E_ARG;
+    }
+    if (!is_device_ptr(counts, b->device)) {
+        HIPCHK(hipMemcpyAsync(b->ft_cin, counts, sizeof(int32_t) * n, hipMemcpyDefault, s));
+        dcin = b->ft_cin;
+        host_in = true;
+    }
+    r = ft_run(b, dsmp, dcin, sample_stride, n, feat, feat_stride, feat_count, flags, s);
+    if (r) return r;
+    if (host_in) HIPCHK(hipStreamSynchronize(s)); /* the caller's host arrays are read until here */
+    return MP3D_OK;
+}
+
+extern "C" int mp3d_batch_feature_time(mp3d_batch *b, float *us) {
+    if (!b || !us || !b->timing || !b->ft_timed) return MP3D_E_ARG;
+    HIPCHK(hipEventSynchronize(b->ev_ft[1]));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, b->ev_ft[0], b->ev_ft[1]));
     *us = ms * 1000.f;
     return MP3D_OK;
 }
