@@ -28,6 +28,7 @@
 #ifndef MP3D_H
 #define MP3D_H
 
+#include <limits.h>
 #include <stddef.h>
 #include <stdint.h>
 
@@ -254,7 +255,47 @@ MP3D_API int mp3d_dec_set_state(mp3d_dec *dec, const void *buf);
  * seen (n0 + T/2 <= inputs seen - 1); the tail waits for the next call.  A
  * stream's resampler restarts (history zero, m = 0) at create, at
  * mp3d_batch_reset, at mp3d_batch_set_state on its slot, at a change of the
- * output format, and after its own flush.                                   */
+ * output format, and after its own flush.
+ *
+ * Sample windows.  Each stream slot of a handle with a packed format set has
+ * a fed count r and a window [lo, hi), both in input samples per channel at
+ * the stream's own rate.  r counts the samples of the audio frame slots the
+ * sink has been fed (0 < samples <= 1152, 1 or 2 channels, after the rate is
+ * known).  Input sample number r of the slot reaches the channel map and the
+ * resampler only if lo <= r < hi; the resampler sees the kept samples as one
+ * contiguous signal, and its time axis, history, emit rule and flush rule
+ * are the ones above with "inputs seen" meaning kept inputs.  r advances by
+ * every sample fed, kept or not, written or not (a stride overflow,
+ * out_count = -1, still advances it).  The input rate is still fixed by the
+ * first audio frame after a resampler restart, kept or trimmed.
+ *
+ * A window restart sets r = 0 and the window to "not fixed".  It happens
+ * where the resampler state is zeroed (create, mp3d_batch_reset,
+ * mp3d_batch_set_state on the slot, mp3d_batch_set_output) and at
+ * mp3d_batch_set_window on the slot.  MP3D_PACK_FLUSH, a stride overflow and
+ * mp3d_batch_set_features are NOT window restarts: they restart the
+ * resampler and the feature state, r and the window carry on (a flush is not
+ * a stream start: a stream flushed mid-file and continued does not have its
+ * head trimmed a second time).
+ *
+ * mp3d_batch_set_window fixes the window at once, and MP3D_PACK_GAPLESS is
+ * then ignored.  Otherwise the window is fixed by the first packed or feature
+ * call after the restart that feeds the slot at least one sample: if that
+ * call carries MP3D_PACK_GAPLESS and the stream's Xing/Info tag has a LAME /
+ * Lavf / Lavc extension, lo = enc_delay + 529 (skip_samples) and hi =
+ * total_frames * spf + 529 - enc_padding (end_sample) when the tag carries a
+ * frame count > 0 and that end is >= 0, else no end: mp3d_stream_info's
+ * values and mp3d_batch_decode_long_packed's trim.  Without the flag or such
+ * a tag the window is [0, no end).  Once fixed, the flag of later calls is
+ * ignored for the slot until its next window restart.  With no flag and no
+ * explicit window every call produces exactly the bits it produced without
+ * windows.  A window only removes samples, so mp3d_packed_max_samples and
+ * mp3d_feat_max_frames stay valid bounds.
+ *
+ * mp3d_batch_set_state leaves the window unfixed with r = 0, so a state
+ * restored mid-file counts from the restore point; a caller moving a stream
+ * mid-file reads its window with mp3d_batch_sink_window and sets
+ * (max(lo - r, 0), max(hi - r, 0)) (no end stays no end) on the destination. */
 
 /* host only, no GPU: taps[L][T] floats (NULL: sizes only); cap = floats taps
  * can hold; returns L * T or MP3D_E_ARG */
@@ -285,12 +326,32 @@ MP3D_API long long mp3d_packed_max_samples(int out_hz, int frames, int min_in_hz
  * MP3D_E_ARG; a host out may sit anywhere.  A host (or other-GPU) out is
  * filled from a staging buffer by one copy of out_count[s] samples per
  * stream, which keeps the bytes past them untouched but costs n_streams
- * copies per call: meant for small batches, wide ones pass device memory.   */
+ * copies per call: meant for small batches, wide ones pass device memory.
+ * flags: MP3D_PACK_FLUSH, MP3D_PACK_GAPLESS (sample windows, above); any
+ * other bit is MP3D_E_ARG.                                                  */
 #define MP3D_PACK_FLUSH 1
+#define MP3D_PACK_GAPLESS 2
 MP3D_API int mp3d_batch_decode_packed(mp3d_batch *b, const uint8_t *frames, const uint64_t *offsets,
                                       const uint32_t *sizes, int n_streams, int frames_per_stream, void *out, int f32,
                                       long long out_stride, int *out_count, int flags, mp3d_frame_info *infos,
                                       void *hip_stream);
+
+/* Fixes the sample windows [lo[i], hi[i]) of slots [first, first + n) (host
+ * arrays of n; hi == NULL: no end for all; an element MP3D_WINDOW_NO_END: no
+ * end for that slot).  lo == NULL && hi == NULL un-fixes them, a plain window
+ * restart.  Either way the slots' resampler state, fed count and (when
+ * features are set) feature state restart first.  Orders after the handle's
+ * last call and returns when done.  MP3D_E_ARG, writing nothing: no packed
+ * format set, lo[i] < 0, hi[i] < lo[i], or hi without lo.  MP3D_E_CAPACITY:
+ * the range is past max_streams.                                            */
+#define MP3D_WINDOW_NO_END LLONG_MAX
+MP3D_API int mp3d_batch_set_window(mp3d_batch *b, int first, int n, const long long *lo, const long long *hi);
+
+/* The slots' windows and fed counts r into host arrays of n; any of the three
+ * may be NULL.  A slot whose window is not fixed reports 0,
+ * MP3D_WINDOW_NO_END, 0.  Orders after the handle's last call and returns
+ * when done, as mp3d_batch_get_state does; errors as above.                 */
+MP3D_API int mp3d_batch_sink_window(mp3d_batch *b, int first, int n, long long *lo, long long *hi, long long *fed);
 
 /* device-side microseconds of the resample stage of the last packed call, or
  * of the last chunk of the last mp3d_batch_decode_long_packed call (a stream
@@ -418,8 +479,10 @@ MP3D_API int mp3d_batch_set_features(mp3d_batch *b, int n_mels, int flags);
  * feat, feat_count and infos (may be NULL) are host or device memory; the
  * call is asynchronous when all of them are device memory, and a host feat is
  * filled by one copy per stream, as the packed call's out is.  flags:
- * MP3D_PACK_FLUSH flushes the resampler, then the features.  MP3D_E_ARG
- * before mp3d_batch_set_features.                                           */
+ * MP3D_PACK_FLUSH flushes the resampler, then the features;
+ * MP3D_PACK_GAPLESS as in the packed call: the frames are centred on
+ * multiples of 160 samples of the windowed signal.  MP3D_E_ARG before
+ * mp3d_batch_set_features.                                                  */
 MP3D_API int mp3d_batch_decode_features(mp3d_batch *b, const uint8_t *frames, const uint64_t *offsets,
                                         const uint32_t *sizes, int n_streams, int frames_per_stream, float *feat,
                                         long long feat_stride, int *feat_count, int flags, mp3d_frame_info *infos,

@@ -55,11 +55,14 @@ EXPORTS = ["mp3d_dec_create", "mp3d_dec_create_on", "mp3d_dec_destroy", "mp3d_de
            "mp3d_dec_set_state", "mp3d_resample_filter", "mp3d_batch_set_output", "mp3d_packed_max_samples",
            "mp3d_batch_decode_packed", "mp3d_batch_resample_time", "mp3d_batch_decode_long_packed",
            "mp3d_long_packed_bound", "mp3d_mel_filterbank", "mp3d_feat_max_frames", "mp3d_batch_set_features",
-           "mp3d_batch_decode_features", "mp3d_batch_features", "mp3d_batch_feature_time"]
+           "mp3d_batch_decode_features", "mp3d_batch_features", "mp3d_batch_feature_time", "mp3d_batch_set_window",
+           "mp3d_batch_sink_window"]
 
 OPT_CRC_CHECK = 1  # MP3D_OPT_CRC_CHECK: drop frames whose CRC-16 mismatches
 LONG_GAPLESS = 1  # MP3D_LONG_GAPLESS: apply the LAME tag's trim inside decode_long_packed
 PACK_FLUSH = 1  # MP3D_PACK_FLUSH: feed zeros after the call's frames, then restart the resamplers
+PACK_GAPLESS = 2  # MP3D_PACK_GAPLESS: fix an unfixed sample window from the stream's LAME tag (decode_packed/_features)
+WINDOW_NO_END = 2**63 - 1  # MP3D_WINDOW_NO_END: a sample window without an end
 FEAT_LOG10 = 1  # MP3D_FEAT_LOG10: log10(max(mel, 1e-10)) instead of the mel energies
 MP3D_FEAT_LOG10 = FEAT_LOG10
 RATES = (8000, 11025, 12000, 16000, 22050, 24000, 32000, 44100, 48000)
@@ -130,6 +133,9 @@ def _bind(L):
     L.mp3d_batch_decode_features.argtypes = [vp, vp, u64p, u32p, i, i, vp, ctypes.c_longlong, vp, i, vp, vp]
     L.mp3d_batch_features.argtypes = [vp, vp, ctypes.c_longlong, vp, i, vp, ctypes.c_longlong, vp, i, vp]
     L.mp3d_batch_feature_time.argtypes = [vp, vp]
+    if hasattr(L, "mp3d_batch_set_window"):  # (an older build loaded for an A/B lacks the two)
+        L.mp3d_batch_set_window.argtypes = [vp, i, i, vp, vp]
+        L.mp3d_batch_sink_window.argtypes = [vp, i, i, vp, vp, vp]
     if hasattr(L, "mp3d_debug_wglds_probe"):  # libmp3d_wglds.so only (tests/test_gpu_wglds.py)
         L.mp3d_debug_wglds_probe.argtypes = [i, i, vp, i]
     return L
@@ -351,15 +357,17 @@ class BatchDecoder:
         self._mels = 0  # a change of the output format turns the feature sink off
 
     def decode_packed(self, frames, offsets, sizes, frames_per_stream, out=None, counts=None, infos=None, f32=True,
-                      flush=False, stride=None, stream=None):
+                      flush=False, stride=None, stream=None, gapless=False):
         """Decode and write every stream's samples contiguously at the rate
         and channel count of set_output (mp3d_batch_decode_packed).  out: None
         (allocate host) or float32 (int16 with f32=False) array/tensor
         [n, stride, channels]; counts: None or int32 array/tensor [n]; infos as
         in decode.  stride defaults to out's, else to the bound that cannot
         overflow.  flush=True ends the streams: the filter tails are emitted
-        and the resamplers restart.  Returns (out, counts, infos); stream s
-        holds counts[s] samples per channel (-1: over the stride)."""
+        and the resamplers restart.  gapless=True fixes the sample window of
+        every stream that has none yet from its LAME tag (set_window).  Returns
+        (out, counts, infos); stream s holds counts[s] samples per channel
+        (-1: over the stride)."""
         off, sz = self._geom(offsets, sizes)
         n, F = off.size, int(frames_per_stream)
         hz, ch = getattr(self, "_out", (0, 0))
@@ -377,9 +385,49 @@ class BatchDecoder:
         cp, k3 = _ptr(counts)
         ip, k4 = _ptr(infos)
         self._ck(self._L.mp3d_batch_decode_packed(self._h, fp, off.ctypes.data, sz.ctypes.data, n, F, op, int(bool(f32)),
-                                              stride, cp, PACK_FLUSH if flush else 0, ip,
+                                              stride, cp,
+                                              (PACK_FLUSH if flush else 0) | (PACK_GAPLESS if gapless else 0), ip,
                                               ctypes.c_void_p(stream) if stream else None))
         return out, counts, infos
+
+    def set_window(self, lo, hi=None, first=0):
+        """Fix the sample windows [lo[i], hi[i]) of streams first, first + 1 ...
+        (mp3d_batch_set_window), in input samples per channel counted from the
+        next sample fed: only those reach the packed and the feature sink.  hi:
+        None (no end for all) or a sequence whose None / WINDOW_NO_END elements
+        mean no end.  lo=None clears the windows of every stream from first on.
+        The streams' resamplers and feature state restart."""
+        first = int(first)
+        if lo is None:
+            if hi is not None:
+                raise ValueError("hi without lo")
+            n = self.max_streams - first
+            self._ck(self._L.mp3d_batch_set_window(self._h, first, n, None, None))
+            return
+        lo = np.ascontiguousarray(lo, np.int64).reshape(-1)
+        n = lo.size
+        hp = None
+        if hi is not None:
+            hi = np.array([WINDOW_NO_END if h is None else int(h) for h in hi], np.int64)
+            if hi.size != n:
+                raise ValueError("lo / hi length mismatch")
+            if (hi < lo).any():
+                raise ValueError("window with hi < lo")
+            hp = hi.ctypes.data
+        if (lo < 0).any():
+            raise ValueError("window with lo < 0")
+        self._ck(self._L.mp3d_batch_set_window(self._h, first, n, lo.ctypes.data, hp))
+
+    def sink_window(self, first=0, n=None):
+        """(lo, hi, fed) of streams [first, first + n): int64 arrays, the
+        sample windows and the samples fed since the last window restart
+        (mp3d_batch_sink_window).  A stream without a fixed window reports
+        (0, WINDOW_NO_END, 0)."""
+        first = int(first)
+        n = self.max_streams - first if n is None else int(n)
+        lo, hi, fed = (np.zeros(max(n, 0), np.int64) for _ in range(3))
+        self._ck(self._L.mp3d_batch_sink_window(self._h, first, n, lo.ctypes.data, hi.ctypes.data, fed.ctypes.data))
+        return lo, hi, fed
 
     def resample_time_us(self):
         """Device-side microseconds of the resample stage of the last packed
@@ -409,14 +457,15 @@ class BatchDecoder:
         return feat, counts, stride
 
     def decode_features(self, frames, offsets, sizes, frames_per_stream, feat=None, counts=None, infos=None,
-                        flush=False, stride=None, stream=None):
+                        flush=False, stride=None, stream=None, gapless=False):
         """Decode as decode_packed does and write every stream's log-mel
         frames (mp3d_batch_decode_features).  feat: None (allocate host) or
         float32 array/tensor [n, stride, n_mels]; counts: None or int32
         array/tensor [n]; infos as in decode.  stride defaults to feat's, else
         to feat_max_frames.  flush=True ends the streams: resampler and
-        feature tails are emitted and both restart.  Returns (feat, counts,
-        infos); stream s holds counts[s] frames (-1: over the stride)."""
+        feature tails are emitted and both restart.  gapless as in
+        decode_packed.  Returns (feat, counts, infos); stream s holds
+        counts[s] frames (-1: over the stride)."""
         off, sz = self._geom(offsets, sizes)
         n, F = off.size, int(frames_per_stream)
         feat, counts, stride = self._feat_args(n, feat, counts, stride, lambda: feat_max_frames(F))
@@ -427,7 +476,7 @@ class BatchDecoder:
         cp, k3 = _ptr(counts)
         ip, k4 = _ptr(infos)
         self._ck(self._L.mp3d_batch_decode_features(self._h, fp, off.ctypes.data, sz.ctypes.data, n, F, op, stride, cp,
-                                                    PACK_FLUSH if flush else 0, ip,
+                                                    (PACK_FLUSH if flush else 0) | (PACK_GAPLESS if gapless else 0), ip,
                                                     ctypes.c_void_p(stream) if stream else None))
         return feat, counts, infos
 

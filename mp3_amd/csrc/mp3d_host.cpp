@@ -49,8 +49,8 @@ void launch_lds_poison(int, hipStream_t);
 void launch_frame(const uint8_t *, uint32_t, const uint64_t *, const uint32_t *, uint8_t *, const uint64_t *,
                   StreamState *, FrameRec *, uint64_t *, void *, int, const DevTables *, int16_t *, UnitMeta *, void *,
                   bool, bool, uint32_t *, uint32_t, hipStream_t);
-void launch_resample(const float *, const void *, RsState *, const RsCfg *, int, const float *, RsPlan *, int32_t *,
-                     void *, bool, int32_t *, int, int, long long, int, int, hipStream_t);
+void launch_resample(const float *, const void *, RsState *, const StreamState *, const RsCfg *, int, const float *,
+                     RsPlan *, int32_t *, void *, bool, int32_t *, int, int, long long, int, int, int, hipStream_t);
 void launch_resample_long(const float *, const void *, const int *, const uint32_t *, const RsCfg *, int, const float *,
                           RsLong *, int32_t *, void *, bool, long long, int, int, int, int, int, int, int, int,
                           hipStream_t);
@@ -2242,7 +2242,8 @@ extern "C" int mp3d_batch_set_output(mp3d_batch *b, int out_hz, int out_channels
 extern "C" int mp3d_batch_decode_packed(mp3d_batch *b, const uint8_t *frames, const uint64_t *offsets,
                                         const uint32_t *sizes, int n, int F, void *out, int f32, long long out_stride,
                                         int *out_count, int flags, mp3d_frame_info *infos, void *hip_stream) {
-    if (!b || !b->rs_hz || !out || !out_count || out_stride < 0 || (flags & ~MP3D_PACK_FLUSH)) return MP3D_E_ARG;
+    if (!b || !b->rs_hz || !out || !out_count || out_stride < 0 || (flags & ~(MP3D_PACK_FLUSH | MP3D_PACK_GAPLESS)))
+        return MP3D_E_ARG;
     if (!frames || !offsets || !sizes || n <= 0 || F <= 0) return MP3D_E_ARG;
     if (n > b->max_streams || F > b->max_frames) return MP3D_E_CAPACITY;
     HIPCHK(hipSetDevice(b->device));
@@ -2275,8 +2276,9 @@ extern "C" int mp3d_batch_decode_packed(mp3d_batch *b, const uint8_t *frames, co
     int32_t *dcnt = cnt_dev ? (int32_t *)out_count : b->rs_cnt;
     if (b->timing) HIPCHK(hipEventRecord(b->ev_rs[0], s));
     if (b->poison) launch_lds_poison(g_dev[b->device].n_cu, s);
-    launch_resample(b->rs_rows, dinf, b->rs_st, b->rs_dcfg, oc, b->rs_tab, b->rs_plan, b->rs_prefix, dout, f32 != 0, dcnt,
-                    n, F, out_dev ? out_stride : stride, (int)tiles, (flags & MP3D_PACK_FLUSH) ? 1 : 0, s);
+    launch_resample(b->rs_rows, dinf, b->rs_st, b->st, b->rs_dcfg, oc, b->rs_tab, b->rs_plan, b->rs_prefix, dout,
+                    f32 != 0, dcnt, n, F, out_dev ? out_stride : stride, (int)tiles, (flags & MP3D_PACK_FLUSH) ? 1 : 0,
+                    (flags & MP3D_PACK_GAPLESS) ? 1 : 0, s);
     if (b->timing) {
         HIPCHK(hipEventRecord(b->ev_rs[1], s));
         b->rs_timed = true;
@@ -2306,6 +2308,60 @@ extern "C" int mp3d_batch_resample_time(mp3d_batch *b, float *us) {
     float ms = 0;
     HIPCHK(hipEventElapsedTime(&ms, b->ev_rs[0], b->ev_rs[1]));
     *us = ms * 1000.f;
+    return MP3D_OK;
+}
+
+/* RsWindow is the head of RsState, r follows it: one strided copy each way */
+static_assert(offsetof(RsState, rate_i) == 0 && offsetof(RsState, fixed) == offsetof(RsWindow, fixed) &&
+                  offsetof(RsState, lo) == offsetof(RsWindow, lo) && offsetof(RsState, hi) == offsetof(RsWindow, hi) &&
+                  offsetof(RsState, r) == sizeof(RsWindow),
+              "RsWindow must mirror the head of RsState");
+
+extern "C" int mp3d_batch_set_window(mp3d_batch *b, int first, int n, const long long *lo, const long long *hi) {
+    if (!b || !b->rs_hz || first < 0 || n <= 0 || (!lo && hi)) return MP3D_E_ARG;
+    if ((long long)first + n > b->max_streams) return MP3D_E_CAPACITY;
+    std::vector<RsWindow> w;
+    if (lo) {
+        w.resize((size_t)n);
+        for (int i = 0; i < n; i++) {
+            const long long h = hi ? hi[i] : MP3D_WINDOW_NO_END;
+            if (lo[i] < 0 || h < lo[i]) return MP3D_E_ARG; /* before anything is written */
+            w[i] = RsWindow{0, 1, lo[i], h};
+        }
+    }
+    HIPCHK(hipSetDevice(b->device));
+    hipStream_t s = b->own;
+    int r = own_after_last(b); /* after the handle's last call, on any stream */
+    if (r) return r;
+    /* a window restart: the slots' resamplers and fed counts restart with it */
+    HIPCHK(hipMemsetAsync(b->rs_st + first, 0, sizeof(RsState) * (size_t)n, s));
+    if (b->ft_st) HIPCHK(hipMemsetAsync(b->ft_st + first, 0, sizeof(FtState) * (size_t)n, s));
+    if (lo)
+        HIPCHK(hipMemcpy2DAsync(b->rs_st + first, sizeof(RsState), w.data(), sizeof(RsWindow), sizeof(RsWindow), (size_t)n,
+                                hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return MP3D_OK;
+}
+
+extern "C" int mp3d_batch_sink_window(mp3d_batch *b, int first, int n, long long *lo, long long *hi, long long *fed) {
+    if (!b || !b->rs_hz || first < 0 || n <= 0) return MP3D_E_ARG;
+    if ((long long)first + n > b->max_streams) return MP3D_E_CAPACITY;
+    struct Head {
+        RsWindow w;
+        int64_t r;
+    };
+    std::vector<Head> h((size_t)n);
+    HIPCHK(hipSetDevice(b->device));
+    int r = own_after_last(b);
+    if (r) return r;
+    HIPCHK(hipMemcpy2DAsync(h.data(), sizeof(Head), b->rs_st + first, sizeof(RsState), sizeof(Head), (size_t)n,
+                            hipMemcpyDeviceToHost, b->own));
+    HIPCHK(hipStreamSynchronize(b->own));
+    for (int i = 0; i < n; i++) {
+        if (lo) lo[i] = h[i].w.fixed ? h[i].w.lo : 0;
+        if (hi) hi[i] = h[i].w.fixed ? h[i].w.hi : MP3D_WINDOW_NO_END;
+        if (fed) fed[i] = h[i].r;
+    }
     return MP3D_OK;
 }
 
@@ -2474,7 +2530,8 @@ static int ft_run(mp3d_batch *b, const float *dsmp, const int32_t *dcin, long lo
 extern "C" int mp3d_batch_decode_features(mp3d_batch *b, const uint8_t *frames, const uint64_t *offsets,
                                           const uint32_t *sizes, int n, int F, float *feat, long long feat_stride,
                                           int *feat_count, int flags, mp3d_frame_info *infos, void *hip_stream) {
-    if (!b || !b->ft_mels || !feat || !feat_count || feat_stride < 0 || (flags & ~MP3D_PACK_FLUSH)) return MP3D_E_ARG;
+    if (!b || !b->ft_mels || !feat || !feat_count || feat_stride < 0 || (flags & ~(MP3D_PACK_FLUSH | MP3D_PACK_GAPLESS)))
+        return MP3D_E_ARG;
     if (!frames || !offsets || !sizes || n <= 0 || F <= 0) return MP3D_E_ARG;
     if (n > b->max_streams || F > b->max_frames) return MP3D_E_CAPACITY;
     HIPCHK(hipSetDevice(b->device));

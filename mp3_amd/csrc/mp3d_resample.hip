@@ -23,6 +23,10 @@
  *    come from the table (at most 87 KB per rate pair, L2 / L1 resident) in
  *    16-byte loads of its phase's row, 4 FMAs per channel for each.
  *  - Equal rates: the staged samples are copied.
+ * A stream's sample window (RsState lo, hi, r: a gapless trim from its tag or
+ * an explicit crop) is applied while staging: k_rs_plan turns it into the
+ * call's skip and kept count, and the filter and the update read kept sample
+ * rel at sample rel + skip of the prefix.
  * These inner loops are rs_tile, shared with the long-stream sink below
  * (k_rsl_plan / k_rsl_filter / k_rsl_carry, mp3d_batch_decode_long_packed):
  * one stream, staged chunk by chunk straight from the segments' rows, with
@@ -48,9 +52,29 @@ __device__ __forceinline__ long long rs_emitted(long long n, const RsFilt &f) {
     return n > f.post ? rs_ceil_div((n - f.post) * f.L, f.M) : 0;
 }
 
+/* The gapless window of a stream from its tag words (StreamState tag_info,
+ * tag_frames, kind): tag_to_info (mp3d_host.cpp), FFmpeg's skip and end of
+ * the LAME tag.  [0, no end) without the flag or a LAME / Lavf / Lavc tag. */
+__device__ __forceinline__ void rs_tag_window(const uint32_t *__restrict__ tag, int gapless, long long &lo, long long &hi) {
+    lo = 0;
+    hi = INT64_MAX;
+    const uint32_t tg = tag[0];
+    if (gapless && (tg & MP3D_TAG_LAME)) {
+        lo = (long long)((tg >> 12) & 0xFFFu) + 529;
+        const int frames = (tg & MP3D_TAG_FRAMES) ? (int)tag[1] : -1;
+        if (frames > 0) {
+            const long long end = (long long)frames * ((int)tag[2] == 2 ? 576 : 1152) + 529 - (long long)(tg & 0xFFFu);
+            if (end >= 0) hi = end;
+        }
+    }
+}
+
+/* st[s]'s window is written here (fixed by the first call that feeds the slot
+ * a sample), the rest of the state by k_rs_update */
 __global__ void __launch_bounds__(MP3D_RS_THREADS)
-k_rs_plan(const DevInfo *__restrict__ inf, const RsState *__restrict__ st, const RsCfg *__restrict__ cfg, RsPlan *__restrict__ plan,
-          int32_t *__restrict__ prefix, int32_t *__restrict__ out_count, int n, int F, long long stride, int flush) {
+k_rs_plan(const DevInfo *__restrict__ inf, RsState *__restrict__ st, const StreamState *__restrict__ sst,
+          const RsCfg *__restrict__ cfg, RsPlan *__restrict__ plan, int32_t *__restrict__ prefix,
+          int32_t *__restrict__ out_count, int n, int F, long long stride, int flush, int gapless) {
     MP3D_LDS_ENTRY();
     const int s = blockIdx.x * MP3D_RS_THREADS + threadIdx.x;
     if (s >= n) return;
@@ -67,16 +91,32 @@ k_rs_plan(const DevInfo *__restrict__ inf, const RsState *__restrict__ st, const
         }
     }
     pf[F] = nin;
+    /* the window: samples [a, b) of the call's nin are kept */
+    long long lo = 0, hi = INT64_MAX;
+    if (st[s].fixed) {
+        lo = st[s].lo;
+        hi = st[s].hi;
+    } else if (nin > 0) {
+        rs_tag_window(&sst[s].tag_info, gapless, lo, hi);
+        st[s].fixed = 1;
+        st[s].lo = lo;
+        st[s].hi = hi;
+    }
+    const long long r = st[s].r;
+    const int a = (int)min(max(lo - r, 0LL), (long long)nin);
+    const int b = (int)min(max(hi - r, (long long)a), (long long)nin);
     RsPlan P;
     P.pos = pos;
     P.m0 = 0;
     P.rate_i = ri;
-    P.n_in = nin;
+    P.n_in = b - a;
     P.count = 0;
     P.restart = flush;
+    P.skip = a;
+    P.fed = nin;
     if (ri) {
         const RsFilt f = cfg->f[ri - 1];
-        const long long n1 = pos + nin;
+        const long long n1 = pos + P.n_in;
         P.m0 = rs_emitted(pos, f);
         const long long m1 = flush ? rs_ceil_div(n1 * f.L, f.M) : rs_emitted(n1, f);
         const long long c = m1 - P.m0;
@@ -250,8 +290,10 @@ k_rs_filter(const float *__restrict__ rows, const DevInfo *__restrict__ inf, con
 #pragma unroll
         for (int c = 0; c < OC; c++) sx[i * OC + c] = rel < 0 && HL + rel >= 0 ? hist[(HL + rel) * OC + c] : 0.0f;
     }
-    const int lo = max(relA, 0), hi = min(relA + len, P.n_in);
+    /* kept samples [lo, hi) - skip of the call, as samples of its prefix */
+    const int lo = max(relA, 0) + P.skip, hi = min(relA + len, P.n_in) + P.skip;
     if (lo < hi) {
+        const int sx0 = -relA - P.skip; /* sample of the prefix -> element of sx */
         const int32_t *pf = prefix + (size_t)s * (F + 1);
         for (int fr = rs_frame_of(pf, F, lo); fr < F; fr++) {
             const int a = pf[fr], b = pf[fr + 1];
@@ -263,7 +305,7 @@ k_rs_filter(const float *__restrict__ rows, const DevInfo *__restrict__ inf, con
                 float v[OC];
                 rs_load<OC>(row, ch, k - a, v);
 #pragma unroll
-                for (int c = 0; c < OC; c++) sx[(k - relA) * OC + c] = v[c];
+                for (int c = 0; c < OC; c++) sx[(k + sx0) * OC + c] = v[c];
             }
         }
     }
@@ -272,7 +314,8 @@ k_rs_filter(const float *__restrict__ rows, const DevInfo *__restrict__ inf, con
                      ((size_t)s * (size_t)stride + (size_t)mA) * OC, t);
 }
 
-/* the state after the call: the last pre + post inputs, the position */
+/* the state after the call: the last pre + post kept inputs, the position,
+ * the fed count */
 template <int OC>
 __global__ void __launch_bounds__(MP3D_RS_THREADS)
 k_rs_update(const float *__restrict__ rows, const DevInfo *__restrict__ inf, RsState *__restrict__ st,
@@ -285,36 +328,41 @@ k_rs_update(const float *__restrict__ rows, const DevInfo *__restrict__ inf, RsS
     if (P.restart) {
         for (int i = t; i < MP3D_RS_HIST * 2; i += MP3D_RS_THREADS) S->hist[i] = 0.0f;
         if (t == 0) {
+            /* the resampler restarts; the window and its count carry on */
             S->rate_i = 0;
-            S->pad_ = 0;
             S->pos = 0;
+            S->r += P.fed;
         }
         return;
     }
-    if (!P.rate_i || !P.n_in) return;
+    if (!P.rate_i || !P.fed) return;
     const RsFilt f = cfg->f[P.rate_i - 1];
-    const int HL = f.pre + f.post;
-    const int32_t *pf = prefix + (size_t)s * (F + 1);
-    for (int i = t; i < HL; i += MP3D_RS_THREADS) {
-        const int rel = P.n_in - HL + i;
-        float v[OC];
-        if (rel < 0) {
+    if (P.n_in) { /* (a call that kept nothing leaves the history as it is) */
+        const int HL = f.pre + f.post;
+        const int32_t *pf = prefix + (size_t)s * (F + 1);
+        for (int i = t; i < HL; i += MP3D_RS_THREADS) {
+            const int rel = P.n_in - HL + i;
+            float v[OC];
+            if (rel < 0) {
 #pragma unroll
-            for (int c = 0; c < OC; c++) v[c] = S->hist[(HL + rel) * OC + c];
-        } else {
-            const int fr = rs_frame_of(pf, F, rel);
-            rs_load<OC>(rows + ((size_t)s * F + fr) * 2304, inf[(size_t)s * F + fr].channels, rel - pf[fr], v);
+                for (int c = 0; c < OC; c++) v[c] = S->hist[(HL + rel) * OC + c];
+            } else {
+                const int k = rel + P.skip;
+                const int fr = rs_frame_of(pf, F, k);
+                rs_load<OC>(rows + ((size_t)s * F + fr) * 2304, inf[(size_t)s * F + fr].channels, k - pf[fr], v);
+            }
+#pragma unroll
+            for (int c = 0; c < OC; c++) nh[i * OC + c] = v[c];
         }
-#pragma unroll
-        for (int c = 0; c < OC; c++) nh[i * OC + c] = v[c];
+        __syncthreads();
+        for (int i = t; i < HL * OC; i += MP3D_RS_THREADS) S->hist[i] = nh[i];
     }
-    __syncthreads();
-    for (int i = t; i < HL * OC; i += MP3D_RS_THREADS) S->hist[i] = nh[i];
     if (t == 0) {
         long long pos = P.pos + P.n_in;
         if (pos >= (long long)f.post + f.M) pos = f.post + (pos - f.post) % f.M;
         S->rate_i = P.rate_i;
         S->pos = pos;
+        S->r += P.fed;
     }
 }
 
@@ -416,18 +464,7 @@ k_rsl_plan(const DevInfo *__restrict__ inf, const int *__restrict__ a, const uin
     prefix[n_out] = n_in;
     long long lo = S->lo, hi = S->hi;
     if (first) {
-        /* tag_to_info (mp3d_host.cpp): FFmpeg's skip and end of the LAME tag */
-        lo = 0;
-        hi = INT64_MAX;
-        const uint32_t tg = tag[0];
-        if (gapless && (tg & MP3D_TAG_LAME)) {
-            lo = (long long)((tg >> 12) & 0xFFFu) + 529;
-            const int frames = (tg & MP3D_TAG_FRAMES) ? (int)tag[1] : -1;
-            if (frames > 0) {
-                const long long end = (long long)frames * ((int)tag[2] == 2 ? 576 : 1152) + 529 - (long long)(tg & 0xFFFu);
-                if (end >= 0) hi = end;
-            }
-        }
+        rs_tag_window(tag, gapless, lo, hi);
         S->lo = lo;
         S->hi = hi;
     }
@@ -562,12 +599,13 @@ void launch_resample_long(const float *rows, const void *infos, const int *a, co
 #undef RSL_FILTER
 }
 
-void launch_resample(const float *rows, const void *infos, RsState *st, const RsCfg *cfg, int out_ch, const float *tab,
-                     RsPlan *plan, int32_t *prefix, void *out, bool f32, int32_t *out_count, int n, int F,
-                     long long stride, int tiles, int flush, hipStream_t strm) {
+void launch_resample(const float *rows, const void *infos, RsState *st, const StreamState *sst, const RsCfg *cfg,
+                     int out_ch, const float *tab, RsPlan *plan, int32_t *prefix, void *out, bool f32,
+                     int32_t *out_count, int n, int F, long long stride, int tiles, int flush, int gapless,
+                     hipStream_t strm) {
     const DevInfo *inf = (const DevInfo *)infos;
     hipLaunchKernelGGL(k_rs_plan, dim3((n + MP3D_RS_THREADS - 1) / MP3D_RS_THREADS), dim3(MP3D_RS_THREADS), 0, strm, inf,
-                       st, cfg, plan, prefix, out_count, n, F, stride, flush);
+                       st, sst, cfg, plan, prefix, out_count, n, F, stride, flush, gapless);
     const dim3 grid((unsigned)n * (unsigned)tiles), blk(MP3D_RS_THREADS);
 #define RS_FILTER(OC, F32)                                                                                             \
     hipLaunchKernelGGL((k_rs_filter<OC, F32>), grid, blk, 0, strm, rows, inf, st, cfg, tab, plan, prefix, out, F, stride, \
