@@ -5,12 +5,7 @@ round set-up, staging, scalefactors, big_values, count1, meta stores; lane
 0 adds them to g_htime with one global atomic per stage at the end;
 mp3d_dbg_ptime() reads and clears them (tools/dbg/huff_stage_times.py).
 Usage: python abx/htime.py"""
-import os
-import shutil
-import sys
-
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from mp3_amd import _build  # noqa: E402
+import stage
 
 T = "__builtin_amdgcn_s_memtime()"
 
@@ -49,22 +44,11 @@ def main():
             "    hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(g_htime), 8 * 8);\n"
             "    unsigned long long z[8] = {};\n    if (!e) e = hipMemcpyToSymbol(HIP_SYMBOL(g_htime), z, 8 * 8);\n"
             "    return e;\n}\n}\n")
-    host = open("mp3_amd/csrc/mp3d_host.cpp").read()
+    host = open("mp3_amd/csrc/" + stage.HOST).read()
     host += ("\nnamespace mp3d { hipError_t dbg_htime(unsigned long long *); }\n"
              "extern \"C\" __attribute__((visibility(\"default\"))) int mp3d_dbg_ptime(unsigned long long *o) "
              "{ return mp3d::dbg_htime(o) ? -1 : 0; }\n")
-    d = "/tmp/vars/HT"
-    os.makedirs(d, exist_ok=True)
-    for h in _build.HIP_HDRS:
-        shutil.copy("mp3_amd/csrc/" + h, d)
-    for k in ("mp3d_demux.hip", "mp3d_synth.hip"):
-        shutil.copy("mp3_amd/csrc/" + k, d)
-    open(d + "/mp3d_huffman.hip", "w").write(src)
-    open(d + "/mp3d_host.cpp", "w").write(host)
-    os.makedirs(d + "/../../include", exist_ok=True)
-    shutil.copy("include/mp3d.h", d + "/../../include/")
-    _build.compile_hip(d, "build_ab/HT.so", d + "/obj")
-    print("build_ab/HT.so")
+    stage.build("/tmp/vars/HT", "build_ab/HT.so", {"mp3d_huffman.hip": src, stage.HOST: host})
 
 
 if __name__ == "__main__":

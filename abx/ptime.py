@@ -5,11 +5,8 @@ phases Q, I, M, W and the loop head, then adds them to g_ptime with one
 global atomic per phase; mp3d_dbg_ptime() reads and clears them
 (tools/dbg/synth_phase_times.py).  Usage: python abx/ptime.py"""
 import os
-import shutil
-import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from mp3_amd import _build  # noqa: E402
+import stage
 
 Q = "            /* ---------------- phase Q: requantise + stereo -> LDS ---------- */"
 I = "            /* ---------------- phase I: alias + IMDCT + overlap ------------ */"
@@ -72,23 +69,12 @@ def main():
             "    hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(g_ptime), 8 * 8);\n"
             "    unsigned long long z[8] = {};\n    if (!e) e = hipMemcpyToSymbol(HIP_SYMBOL(g_ptime), z, 8 * 8);\n"
             "    return e;\n}\n}\n")
-    host = open("mp3_amd/csrc/mp3d_host.cpp").read()
+    host = open("mp3_amd/csrc/" + stage.HOST).read()
     host += ("\nnamespace mp3d { hipError_t dbg_ptime(unsigned long long *); }\n"
              "extern \"C\" __attribute__((visibility(\"default\"))) int mp3d_dbg_ptime(unsigned long long *o) "
              "{ return mp3d::dbg_ptime(o) ? -1 : 0; }\n")
-    d = "/tmp/vars/PT"
-    os.makedirs(d, exist_ok=True)
-    for h in _build.HIP_HDRS:
-        shutil.copy("mp3_amd/csrc/" + h, d)
-    for k in ("mp3d_demux.hip", "mp3d_huffman.hip"):
-        shutil.copy("mp3_amd/csrc/" + k, d)
-    open(d + "/mp3d_synth.hip", "w").write(src)
-    open(d + "/mp3d_host.cpp", "w").write(host)
-    os.makedirs(d + "/../../include", exist_ok=True)
-    shutil.copy("include/mp3d.h", d + "/../../include/")
     out = {"prefetch": "build_ab/PT2.so", "w": "build_ab/PTW.so"}.get(mark, "build_ab/PT.so")
-    _build.compile_hip(d, out, d + "/obj")
-    print(out)
+    stage.build("/tmp/vars/PT", out, {"mp3d_synth.hip": src, stage.HOST: host})
 
 
 if __name__ == "__main__":

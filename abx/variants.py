@@ -1,12 +1,9 @@
 #!/usr/bin/env python3
 """Build k_synth phase-ablation variants (build_ab/NAME.so) for A/B timing only:
 their output is wrong by construction.  Usage: python abx/variants.py"""
-import os
-import shutil
 import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from mp3_amd import _build  # noqa: E402
+import stage
 
 KERNELS = ["mp3d_demux.hip", "mp3d_huffman.hip", "mp3d_synth.hip", "mp3d_demux_dev.h", "mp3d_huffman_dev.h", "mp3d_internal.h"]
 
@@ -18,16 +15,7 @@ def variant(name, reps):
     for a, b in reps:
         assert any(a in s for s in srcs.values()), (name, a)
         srcs = {k: s.replace(a, b) for k, s in srcs.items()}
-    d = "/tmp/vars/" + name
-    os.makedirs(d, exist_ok=True)
-    for h in _build.HIP_HDRS:
-        shutil.copy("mp3_amd/csrc/" + h, d)
-    for k, s in srcs.items():
-        open(d + "/" + k, "w").write(s)
-    shutil.copy("mp3_amd/csrc/mp3d_host.cpp", d)
-    os.makedirs(d + "/../../include", exist_ok=True)
-    shutil.copy("include/mp3d.h", d + "/../../include/")
-    _build.compile_hip(d, "build_ab/%s.so" % name, d + "/obj", extra=flags)
+    stage.build("/tmp/vars/" + name, "build_ab/%s.so" % name, srcs, extra=flags)
 
 
 W4H = ("__global__ void __launch_bounds__(HUFF_BLOCK) k_huffman(",
@@ -263,8 +251,8 @@ VARS = {
     "NOW3": [],
     # r02 diagnostic (same output): k_frame phase timestamps (s_memtime) in g_fdbg, read by
     # tools/dbg/frame_timing.py through mp3d_dbg_read
-    "FRT": [("#define PF_BYTES 4096 /* = MP3D_PF_BYTES (mp3d_host.cpp): the staged stream length */\n",
-             "#define PF_BYTES 4096 /* = MP3D_PF_BYTES (mp3d_host.cpp): the staged stream length */\n"
+    "FRT": [("#define PF_BYTES 4096 /* = MP3D_PF_BYTES (mp3d_dec.cpp): the staged stream length */\n",
+             "#define PF_BYTES 4096 /* = MP3D_PF_BYTES (mp3d_dec.cpp): the staged stream length */\n"
              "__device__ unsigned long long g_fdbg[32];\n"
              "#define FT(i) do { __asm__ volatile(\"s_waitcnt vmcnt(0) lgkmcnt(0)\" ::: \"memory\"); const unsigned long long t_ = __builtin_amdgcn_s_memtime(); if (lane == 0) g_fdbg[(i)] = t_; } while (0)\n"),
             ("    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);\n    if (wv == 0) {\n",

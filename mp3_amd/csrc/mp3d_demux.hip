@@ -6,6 +6,7 @@
  * Pipeline overview: mp3d_device.h.
  */
 #include "mp3d_demux_dev.h"
+#include "mp3d_launch.h"
 
 namespace mp3d {
 
@@ -483,7 +484,7 @@ hipError_t upload_demux_constants(const uint16_t *frame_bytes) { return upload_d
  * per stream (fewer launches: the per-frame decoder, small batches) */
 /* ------------------------------------------------------------------------ */
 /* k_demux_fp: one stream's run of pre-located, complete frames (the per-  */
-/* frame decoder's read-ahead runs, mp3d_host.cpp ra_fill: the host has     */
+/* frame decoder's read-ahead runs, mp3d_dec.cpp ra_fill: the host has      */
 /* found every frame, fo[f] = its header offset in the run's bytes, passed  */
 /* as kernel arguments) demuxed frame-parallel in ONE workgroup, with the   */
 /* same results as k_demux: the run's bytes are staged in LDS, wave 0       */

@@ -28,6 +28,7 @@
  */
 #include "mp3d_device.h"
 #include "mp3d_features.h"
+#include "mp3d_launch.h"
 
 /* A frame's bits may not depend on which copy of a loop body the compiler
  * runs it in (peeled, unrolled, remainder): no implicit contraction, every

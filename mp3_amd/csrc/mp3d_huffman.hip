@@ -7,6 +7,7 @@
 #include <algorithm>
 
 #include "mp3d_huffman_dev.h"
+#include "mp3d_launch.h"
 
 namespace mp3d {
 

@@ -1,6 +1,7 @@
 /*
  * mp3d_internal.h -- device data layout shared by the HIP kernels
- * (mp3d_demux.hip, mp3d_huffman.hip, mp3d_synth.hip) and the host library (mp3d_host.cpp).
+ * (mp3d_demux.hip, mp3d_huffman.hip, mp3d_synth.hip) and the host library (mp3d_batch.cpp
+ * and the other host sources, mp3d_host.h).
  *
  * HBM layout of one batch (SoA, one process per GPU):
  *   input   : caller's frame bytes, stream s at in_off[s] (u64), in_len[s]
@@ -30,7 +31,7 @@
 
 /* MPEG-1 pretab (ISO Table B.6, MP3D_PRETAB in mp3d_tables.h) as 2 bits
  * per long band, for lane-indexed use without a memory load; checked
- * against the table when the device is initialised (mp3d_host.cpp). */
+ * against the table when the device is initialised (mp3d_host_tables.cpp). */
 #define MP3D_PRETAB_BITS 0x2fe95400000ull
 
 /* Per-frame record written by k_demux. */

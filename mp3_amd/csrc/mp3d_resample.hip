@@ -34,6 +34,7 @@
  */
 #include "mp3d_device.h"
 #include "mp3d_resample.h"
+#include "mp3d_launch.h"
 
 namespace mp3d {
 
@@ -53,7 +54,7 @@ __device__ __forceinline__ long long rs_emitted(long long n, const RsFilt &f) {
 }
 
 /* The gapless window of a stream from its tag words (StreamState tag_info,
- * tag_frames, kind): tag_to_info (mp3d_host.cpp), FFmpeg's skip and end of
+ * tag_frames, kind): tag_to_info (mp3d_batch.cpp), FFmpeg's skip and end of
  * the LAME tag.  [0, no end) without the flag or a LAME / Lavf / Lavc tag. */
 __device__ __forceinline__ void rs_tag_window(const uint32_t *__restrict__ tag, int gapless, long long &lo, long long &hi) {
     lo = 0;

@@ -13,6 +13,7 @@
 #define MP3D_DEMUX_TU frame_tu
 #include "mp3d_demux_dev.h"
 #include "mp3d_huffman_dev.h"
+#include "mp3d_launch.h"
 
 namespace mp3d {
 
@@ -1483,7 +1484,7 @@ __device__ __forceinline__ void synth_stream(const FrameRec *__restrict__ rec, c
      * first one may still be reading the state, so it goes to st_tail (the
      * overlap + fifo tail of StreamState, packed per stream): the next
      * synth-only call reads it from there (st_tail_in), any other use of the
-     * handle first copies it into StreamState (mp3d_host.cpp flush_tail). */
+     * handle first copies it into StreamState (mp3d_batch.cpp flush_tail). */
     if (f1 == F && PF != 1) {
         const int lane = opaque((int)(threadIdx.x & 63)); /* lane values re-derived: not held across the loop */
         const int ch = lane >> 5, sb = lane & 31;
@@ -1632,7 +1633,7 @@ __global__ void __launch_bounds__(256) k_gather_frames(const uint4 *__restrict__
 /* batch's device buffers exactly as the three-kernel path does, so the     */
 /* results are the same bit for bit (tests/test_gpu_per_frame.py).          */
 /* ------------------------------------------------------------------------ */
-#define PF_BYTES 4096 /* = MP3D_PF_BYTES (mp3d_host.cpp): the staged stream length */
+#define PF_BYTES 4096 /* = MP3D_PF_BYTES (mp3d_dec.cpp): the staged stream length */
 
 template <bool F32, bool LSF>
 __global__ void __launch_bounds__(256) k_frame(const uint8_t *__restrict__ in_host, uint32_t in_have,
@@ -1816,7 +1817,7 @@ void launch_synth_xr(const float *xr, const uint8_t *bt, const uint8_t *mixed, c
                        (const uint32_t *)nullptr, 0u);
 }
 
-/* MP3D_DEBUG_POISON only (mp3d_host.cpp poison_env): fill the whole LDS of
+/* MP3D_DEBUG_POISON only (mp3d_batch.cpp poison_env): fill the whole LDS of
  * every CU with 0xFF before each of the handle's launches, so the first
  * workgroup the next kernel places on a CU finds all-ones words (NaN as
  * float) in any LDS it reads before writing, on every run -- not whatever
@@ -1851,7 +1852,7 @@ __global__ void __launch_bounds__(1024) k_lds_pattern(uint32_t word) {
     lds_fill_all(s, word);
 }
 
-/* The debug build's positive control (mp3d_debug_wglds_probe, mp3d_host.cpp;
+/* The debug build's positive control (mp3d_debug_wglds_probe, mp3d_batch.cpp;
  * tests/test_gpu_wglds.py): after a launch that left 0x5A5A5A5A in the LDS of
  * the CUs, every one of n_groups small workgroups runs MP3D_LDS_ENTRY() and
  * copies its whole static LDS allocation to out[group][WGLDS_PROBE_WORDS],

@@ -322,6 +322,35 @@ def test_argument_errors(batch):
     assert counts.max() > 0
 
 
+def test_off_and_on_again(batch, decoded):
+    """Each sink turned off (its buffers freed) and on again: the features
+    off and on, then the output format changed and back with the features set
+    again.  After each, the same flushed call on a reset decoder state gives
+    the bits of a fresh handle."""
+    n_mels, log = 80, True
+    frames, fc, infos, _ = decoded[(n_mels, log)]
+    offs, sizes = batch.geom(0, FS)
+    dec = handle(batch.n, n_mels, log, F=FS)
+
+    def call(what):
+        feat = np.full((batch.n, mp3_amd.feat_max_frames(FS), n_mels), PATTERN, np.float32)
+        feat, got, inf = dec.decode_features(batch.blob, offs, sizes, FS, feat=feat, flush=True)
+        assert np.array_equal(got, fc) and np.array_equal(inf, infos), what
+        for s in range(batch.n):
+            assert same_bits(feat[s, : got[s]], frames[s]) and (feat[s, got[s]:] == PATTERN).all(), (what, s)
+
+    call("first")
+    dec.set_features(0)
+    dec.reset()
+    dec.set_features(n_mels, log10=log)
+    call("features off and on")
+    dec.set_output(48000, 2)
+    dec.set_output(16000, 1)
+    dec.reset()
+    dec.set_features(n_mels, log10=log)
+    call("another output format and back")
+
+
 def test_reset_and_set_state_restart_their_slots():
     x = signals()["noise"]
     nm = 80

@@ -302,6 +302,22 @@ def test_state_rules(batch):
     assert np.array_equal(got_inf, want_inf) and np.array_equal(got.view(np.uint32), want.view(np.uint32))
 
 
+def test_off_and_on_again(batch, expected):
+    """The sink turned off (its buffers freed) and on again with the same
+    format: the same flushed call, on a reset decoder state, gives the bits of
+    a fresh handle."""
+    fmt = (48000, 2)
+    fresh, fresh_counts, _ = run_whole(batch, fmt)
+    dec = mp3_amd.BatchDecoder(batch.n, batch.F)
+    for turn in range(2):
+        out, counts, _ = run_whole(batch, fmt, dec=dec)  # (sets the format: on)
+        assert np.array_equal(counts, fresh_counts), turn
+        assert np.array_equal(out.view(np.uint32), fresh.view(np.uint32)), turn
+        dec.set_output(0, 0)
+        dec.reset()  # the decoder state only: the sink is off
+    check_values(batch, expected, fmt, out, counts)
+
+
 def test_stride_overflow(batch, expected):
     """Stride = the bound for 16 frames of MPEG-1 input: a stream whose output
     exceeds it gets -1, writes nothing and restarts; the others are

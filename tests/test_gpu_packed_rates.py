@@ -3,7 +3,7 @@ packed sinks -- 9 x 9 rates x {1, 2} output channels -- and k_rs_plan on more
 than one block.
 
 The batch is the nine 16-frame goldens, one per input rate, and an empty
-stream.  rs_build (mp3d_host.cpp) never lets a tile span more than
+stream.  rs_build (mp3d_sinks.cpp) never lets a tile span more than
 MP3D_RS_SPAN - T - 2 <= 4 046 input samples, so 16 x 576 = 9 216 inputs are at
 least three tiles of k_rs_filter for every pair: sixteen frames is the smallest
 stream that runs first, inner and last tiles everywhere.  Each pair has its

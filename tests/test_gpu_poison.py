@@ -1,6 +1,6 @@
 """GPU: the first-call suites with every buffer poisoned (VERDICT r05 "do this" 1).
 
-MP3D_DEBUG_POISON=1 (read when a handle is created, mp3d_host.cpp poison_env)
+MP3D_DEBUG_POISON=1 (read when a handle is created, mp3d_batch.cpp poison_env)
 fills every device and pinned allocation of the handle with 0xFF when it is
 made -- at create and at every grow() -- before the zeroing the code does on
 purpose, and fills the whole LDS of every CU with 0xFF before each of the
@@ -292,6 +292,11 @@ def test_poison_packed_values_and_counts(packed, fmt):
 def test_poison_packed_chunking(packed):
     batch, plain, _ = packed
     PK.test_chunking_is_bit_identical(batch, plain, (44100, 2))
+
+
+def test_poison_packed_off_and_on_again(packed):
+    batch, _, expected = packed
+    PK.test_off_and_on_again(batch, expected)
 
 
 # ---- every test above once more under the wglds build: a twin function with

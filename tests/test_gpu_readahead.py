@@ -1,4 +1,4 @@
-"""The per-frame call's read-ahead (mp3d_host.cpp
+"""The per-frame call's read-ahead (mp3d_dec.cpp
 ra_fill / ra_settle): one call decodes up to 16 of the frames in the
 caller's buffer in one batch call, the next calls are served from it after
 a byte check.  Every output must be bit-identical to the single-frame path

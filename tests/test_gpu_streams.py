@@ -78,7 +78,7 @@ def test_state_buffer_size_checks():
 
 
 def test_geometry_cache_large_batch():
-    """The geometry cache (mp3d_host.cpp prepare_geometry) at more than 1 024
+    """The geometry cache (mp3d_batch.cpp prepare_geometry) at more than 1 024
     streams: a call with the same offsets and sizes skips the staging copy, a
     call that changes them (same count) stages again.  Three calls on one
     handle -- batch A, batch B with A's geometry but other bytes, batch C with
