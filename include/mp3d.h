@@ -340,7 +340,7 @@ MP3D_API int mp3d_batch_decode_packed(mp3d_batch *b, const uint8_t *frames, cons
  * arrays of n; hi == NULL: no end for all; an element MP3D_WINDOW_NO_END: no
  * end for that slot).  lo == NULL && hi == NULL un-fixes them, a plain window
  * restart.  Either way the slots' resampler state, fed count and (when
- * features are set) feature state restart first.  Orders after the handle's
+ * features or loudness are set) feature and loudness state restart first.  Orders after the handle's
  * last call and returns when done.  MP3D_E_ARG, writing nothing: no packed
  * format set, lo[i] < 0, hi[i] < lo[i], or hi without lo.  MP3D_E_CAPACITY:
  * the range is past max_streams.                                            */
@@ -502,6 +502,124 @@ MP3D_API int mp3d_batch_features(mp3d_batch *b, const float *samples, long long 
 /* device-side microseconds of the feature stage of the last feature call;
  * needs mp3d_batch_set_timing */
 MP3D_API int mp3d_batch_feature_time(mp3d_batch *b, float *us);
+
+/* ---- loudness sink (ITU-R BS.1770-4 / EBU R128 measurement) --------------- *
+ * Input signal of a stream: its packed-sink output in the handle's format
+ * (out_hz, out_channels 1 or 2, float32 interleaved): x_c[0 .. N) since the
+ * stream's last loudness restart.  Sample windows and MP3D_PACK_GAPLESS act
+ * before it, as for the features.  A stereo -> mono map of 0.5f * (l + r) is
+ * measured as it is: a mono signal reads 3.01 dB below the same signal on two
+ * channels, which is BS.1770's own behaviour.
+ *
+ * K-weighting: two biquads per channel, coefficients computed on the host in
+ * double for fs = out_hz:
+ *   stage 1 (shelf): f0 = 1681.974450955533, G = 3.999843853973347 dB,
+ *                    Q = 0.7071752369554196
+ *     K = tan(pi f0 / fs), Vh = 10^(G/20), Vb = Vh^0.4996667741545416,
+ *     a0 = 1 + K/Q + K^2
+ *     b = [(Vh + Vb K/Q + K^2), 2 (K^2 - Vh), (Vh - Vb K/Q + K^2)] / a0
+ *     a = [1, 2 (K^2 - 1) / a0, (1 - K/Q + K^2) / a0]
+ *   stage 2 (high-pass): f0 = 38.13547087602444, Q = 0.5003270373238773,
+ *     K = tan(pi f0 / fs), a0 = 1 + K/Q + K^2
+ *     b = [1, -2, 1],  a = [1, 2 (K^2 - 1) / a0, (1 - K/Q + K^2) / a0]
+ * (at 48 000 Hz the BS.1770 table).  Each stage is transposed direct form II
+ * in double; with v the float32 sample widened to double:
+ *   o = b0 v + s1;  s1 = b1 v - a1 o + s2;  s2 = b2 v - a2 o
+ * Stage 2 takes stage 1's o, and y_c is stage 2's o.
+ *
+ * Blocks: H = (out_hz + 5) / 10 samples (integer division), 100 ms.
+ *   z[b] = sum_c (1/H) sum_{i = bH .. (b+1)H - 1} y_c[i]^2
+ * accumulated in double, stored as float32.  Momentary loudness is 4 blocks,
+ * short-term 30 blocks: -0.691 + 10 log10(mean z).
+ *
+ * Emit rule: block b is emitted once sample (b+1)H - 1 has been seen, so after
+ * N samples a stream has emitted floor(N / H) blocks.  MP3D_PACK_FLUSH drops
+ * the incomplete block (BS.1770 ignores incomplete blocks) and restarts the
+ * stream's loudness state.  A stream that would exceed block_stride gets
+ * count -1, writes nothing and restarts.
+ *
+ * Peak: peak[s] = max |x_c[i]| over the channels and the samples fed in this
+ * call, float32, exact; 0 for an empty call.  (Sample peak, not true peak.)
+ *
+ * Integrated loudness of a block sequence z[0 .. n):
+ *   G[j] = (z[j] + z[j+1] + z[j+2] + z[j+3]) / 4, j = 0 .. n - 4
+ *   l[j] = -0.691 + 10 log10 G[j];  J1 = {j : l[j] > -70}
+ *   Gamma = -0.691 + 10 log10(mean_{J1} G) - 10
+ *   result = -0.691 + 10 log10(mean_{j in J1, l[j] > Gamma} G[j])
+ * in double; -HUGE_VAL when n < 4 or no block passes.
+ *
+ * Numerical contract: a tolerance, not bits (the filter runs parallel in time
+ * through its state-space form, and the order of its additions depends on
+ * where a call's tiles fall).  The same call on the same state gives the same
+ * bits every time.  Against the definition above evaluated in float64, with C
+ * the channel count and P the largest |x| of the stream since its restart,
+ *   |z - ref| <= 2^-22 ref + 1e-9 * C * P^2.
+ *
+ * The per-stream loudness state (a sample count, 2 x 4 doubles of filter
+ * state, the open block's partial sum) lives in the handle while loudness is
+ * set, not in the state blob.  It restarts where the feature state does: at
+ * create, at mp3d_batch_reset, at mp3d_batch_set_state on its slot, at
+ * mp3d_batch_set_output (which also turns loudness off), at
+ * mp3d_batch_set_loudness, at mp3d_batch_set_window on its slot, after its
+ * own flush and after an overflow.  Features and loudness may both be on.   */
+
+/* host only, no GPU: coef[10] = b0 b1 b2 a1 a2 of stage 1, then of stage 2
+ * (NULL: size only); cap = doubles coef can hold; returns 10, or MP3D_E_ARG
+ * for a rate outside the nine or a short cap */
+MP3D_API long long mp3d_loudness_filter(int hz, double *coef, size_t cap);
+
+/* host only: a block_stride that can never overflow for one call of `frames`
+ * frames per stream of input rate >= min_in_hz: floor((H - 1 + S) / H) with
+ * S = mp3d_packed_max_samples(out_hz, frames, min_in_hz); 0 when S is 0 */
+MP3D_API long long mp3d_loud_max_blocks(int out_hz, int frames, int min_in_hz);
+
+/* Needs a packed format (mp3d_batch_set_output), else MP3D_E_ARG.  on != 0
+ * uploads the coefficients and the state-transition tables of the format's
+ * rate, restarts every slot's loudness state and waits for the handle's
+ * work; on = 0 turns the sink off and frees its buffers. */
+MP3D_API int mp3d_batch_set_loudness(mp3d_batch *b, int on);
+
+/* The stage itself: feeds counts[s] (clamped to [0, sample_stride]) sample
+ * frames from samples + s * sample_stride * out_channels per stream through
+ * the slots' loudness state; stream s writes block_count[s] block energies at
+ * blocks + s * block_stride, nothing past them, and peak[s] (peak may be
+ * NULL).  samples and counts are host or device memory (a host samples array
+ * is read whole); blocks, block_count and peak are host or device memory, the
+ * call is asynchronous when all three are device memory, and a host blocks is
+ * filled by one copy per stream.  Device pointers must be float-aligned, else
+ * MP3D_E_ARG.  flags: MP3D_PACK_FLUSH only.  This is what a caller runs on the
+ * device out and out_count of mp3d_batch_decode_packed (float32), or on the
+ * device output of mp3d_batch_decode_long_packed with n_streams = 1, without
+ * decoding twice.  Leaves the decoder and resampler state untouched.
+ * MP3D_E_ARG before mp3d_batch_set_loudness.                                */
+MP3D_API int mp3d_batch_loudness(mp3d_batch *b, const float *samples, long long sample_stride, const int *counts,
+                                 int n_streams, float *blocks, long long block_stride, int *block_count, float *peak,
+                                 int flags, void *hip_stream);
+
+/* Decodes exactly as mp3d_batch_decode_packed does (decoder and resampler
+ * state advance exactly so) into a handle-owned float32 sample buffer of
+ * stride mp3d_packed_max_samples(out_hz, frames_per_stream, 0) with device
+ * counts, then runs the stage on it: for scanning a corpus whose PCM is not
+ * wanted.  flags: MP3D_PACK_FLUSH | MP3D_PACK_GAPLESS, both forwarded (the
+ * flush ends the resampler, then drops the open block).                     */
+MP3D_API int mp3d_batch_decode_loudness(mp3d_batch *b, const uint8_t *frames, const uint64_t *offsets,
+                                        const uint32_t *sizes, int n_streams, int frames_per_stream, float *blocks,
+                                        long long block_stride, int *block_count, float *peak, int flags,
+                                        mp3d_frame_info *infos, void *hip_stream);
+
+/* host only: the integrated loudness of z[0 .. n) as defined above */
+MP3D_API int mp3d_loudness_integrated(const float *z, long long n, double *lufs);
+
+/* The same gating on the device for n_streams rows blocks + s * block_stride
+ * of counts[s] blocks each, so a normalisation gain never leaves the GPU:
+ * lufs[s] as float32, -INFINITY for a count of -1 or < 4 or when no block
+ * passes.  Host or device pointers, as above.  Needs mp3d_batch_set_loudness. */
+MP3D_API int mp3d_batch_loudness_integrated(mp3d_batch *b, const float *blocks, long long block_stride,
+                                            const int *counts, int n_streams, float *lufs, void *hip_stream);
+
+/* device-side microseconds of the loudness stage of the last loudness call;
+ * needs mp3d_batch_set_timing */
+MP3D_API int mp3d_batch_loudness_time(mp3d_batch *b, float *us);
 
 /* ---- diagnostics -------------------------------------------------------- */
 MP3D_API const char *mp3d_strerror(int err);

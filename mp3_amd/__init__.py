@@ -56,7 +56,9 @@ EXPORTS = ["mp3d_dec_create", "mp3d_dec_create_on", "mp3d_dec_destroy", "mp3d_de
            "mp3d_batch_decode_packed", "mp3d_batch_resample_time", "mp3d_batch_decode_long_packed",
            "mp3d_long_packed_bound", "mp3d_mel_filterbank", "mp3d_feat_max_frames", "mp3d_batch_set_features",
            "mp3d_batch_decode_features", "mp3d_batch_features", "mp3d_batch_feature_time", "mp3d_batch_set_window",
-           "mp3d_batch_sink_window"]
+           "mp3d_batch_sink_window", "mp3d_loudness_filter", "mp3d_loud_max_blocks", "mp3d_batch_set_loudness",
+           "mp3d_batch_loudness", "mp3d_batch_decode_loudness", "mp3d_loudness_integrated",
+           "mp3d_batch_loudness_integrated", "mp3d_batch_loudness_time"]
 
 OPT_CRC_CHECK = 1  # MP3D_OPT_CRC_CHECK: drop frames whose CRC-16 mismatches
 LONG_GAPLESS = 1  # MP3D_LONG_GAPLESS: apply the LAME tag's trim inside decode_long_packed
@@ -136,6 +138,17 @@ def _bind(L):
     if hasattr(L, "mp3d_batch_set_window"):  # (an older build loaded for an A/B lacks the two)
         L.mp3d_batch_set_window.argtypes = [vp, i, i, vp, vp]
         L.mp3d_batch_sink_window.argtypes = [vp, i, i, vp, vp, vp]
+    if hasattr(L, "mp3d_batch_set_loudness"):  # (an older build loaded for an A/B lacks the loudness sink)
+        L.mp3d_loudness_filter.argtypes = [i, vp, ctypes.c_size_t]
+        L.mp3d_loudness_filter.restype = ctypes.c_longlong
+        L.mp3d_loud_max_blocks.argtypes = [i, i, i]
+        L.mp3d_loud_max_blocks.restype = ctypes.c_longlong
+        L.mp3d_batch_set_loudness.argtypes = [vp, i]
+        L.mp3d_batch_loudness.argtypes = [vp, vp, ctypes.c_longlong, vp, i, vp, ctypes.c_longlong, vp, vp, i, vp]
+        L.mp3d_batch_decode_loudness.argtypes = [vp, vp, u64p, u32p, i, i, vp, ctypes.c_longlong, vp, vp, i, vp, vp]
+        L.mp3d_loudness_integrated.argtypes = [vp, ctypes.c_longlong, ctypes.POINTER(ctypes.c_double)]
+        L.mp3d_batch_loudness_integrated.argtypes = [vp, vp, ctypes.c_longlong, vp, i, vp, vp]
+        L.mp3d_batch_loudness_time.argtypes = [vp, vp]
     if hasattr(L, "mp3d_debug_wglds_probe"):  # libmp3d_wglds.so only (tests/test_gpu_wglds.py)
         L.mp3d_debug_wglds_probe.argtypes = [i, i, vp, i]
     return L
@@ -355,6 +368,7 @@ class BatchDecoder:
         self._ck(self._L.mp3d_batch_set_output(self._h, int(hz), int(channels)))
         self._out = (int(hz), int(channels))
         self._mels = 0  # a change of the output format turns the feature sink off
+        self._loud = False  # and the loudness sink
 
     def decode_packed(self, frames, offsets, sizes, frames_per_stream, out=None, counts=None, infos=None, f32=True,
                       flush=False, stride=None, stream=None, gapless=False):
@@ -502,6 +516,98 @@ class BatchDecoder:
         call (after set_timing)."""
         t = ctypes.c_float()
         self._ck(self._L.mp3d_batch_feature_time(self._h, ctypes.byref(t)))
+        return float(t.value)
+
+    def set_loudness(self, on=True):
+        """Turn the loudness sink on or off (mp3d_batch_set_loudness): ITU-R
+        BS.1770-4 K-weighted 100 ms block energies and the sample peak of the
+        packed output, whatever its format.  Needs set_output.  Restarts every
+        stream's loudness state."""
+        self._ck(self._L.mp3d_batch_set_loudness(self._h, int(bool(on))))
+        self._loud = bool(on)
+
+    def _loud_args(self, n, blocks, counts, peak, stride, default_stride):
+        if stride is None:  # (loudness off: the call fails with MP3D_E_ARG)
+            stride = int(blocks.shape[1]) if blocks is not None else default_stride() if getattr(self, "_loud", 0) else 1
+        stride = int(stride)
+        if blocks is None:
+            blocks = np.zeros((n, stride), np.float32)
+        if counts is None:
+            counts = np.zeros(n, np.int32)
+        if peak is None:
+            peak = np.zeros(n, np.float32)
+        return blocks, counts, peak, stride
+
+    def loudness(self, samples, counts, blocks=None, block_counts=None, peak=None, flush=False, stride=None,
+                 stream=None):
+        """The loudness stage alone (mp3d_batch_loudness): samples float32
+        [n, sample_stride, channels] in the packed format, counts int32 [n]
+        sample frames per stream (both host arrays or device tensors), e.g.
+        the device out and counts of decode_packed.  blocks: None (allocate
+        host) or float32 array/tensor [n, stride]; block_counts int32 [n]; peak
+        float32 [n].  flush=True drops the open block and restarts the streams.
+        Returns (blocks, block_counts, peak): stream s holds block_counts[s]
+        block energies (-1: over the stride)."""
+        n, ss = int(samples.shape[0]), int(samples.shape[1])
+        if not hasattr(counts, "data_ptr"):
+            counts = np.ascontiguousarray(counts, np.int32)
+        H = (getattr(self, "_out", (0, 0))[0] + 5) // 10
+        blocks, block_counts, peak, stride = self._loud_args(n, blocks, block_counts, peak, stride,
+                                                             lambda: (H - 1 + ss) // H)
+        sp, k1 = _ptr(samples)
+        cp, k2 = _ptr(counts)
+        op, k3 = _ptr(blocks)
+        bc, k4 = _ptr(block_counts)
+        pp, k5 = _ptr(peak)
+        self._ck(self._L.mp3d_batch_loudness(self._h, sp if ss else None, ss, cp, n, op, stride, bc, pp,
+                                             PACK_FLUSH if flush else 0, ctypes.c_void_p(stream) if stream else None))
+        return blocks, block_counts, peak
+
+    def decode_loudness(self, frames, offsets, sizes, frames_per_stream, blocks=None, counts=None, peak=None,
+                        infos=None, flush=False, stride=None, stream=None, gapless=False):
+        """Decode as decode_packed does and write every stream's block
+        energies and sample peak (mp3d_batch_decode_loudness).  stride
+        defaults to blocks', else to loud_max_blocks.  flush and gapless as in
+        decode_packed; the flush also drops the open block.  Returns (blocks,
+        counts, peak, infos)."""
+        off, sz = self._geom(offsets, sizes)
+        n, F = off.size, int(frames_per_stream)
+        hz = getattr(self, "_out", (0, 0))[0]
+        blocks, counts, peak, stride = self._loud_args(n, blocks, counts, peak, stride, lambda: loud_max_blocks(hz, F))
+        if infos is None:
+            infos = np.zeros((n, F), FRAME_INFO_DT)
+        fp, k1 = _ptr(frames)
+        op, k2 = _ptr(blocks)
+        cp, k3 = _ptr(counts)
+        pp, k4 = _ptr(peak)
+        ip, k5 = _ptr(infos)
+        self._ck(self._L.mp3d_batch_decode_loudness(self._h, fp, off.ctypes.data, sz.ctypes.data, n, F, op, stride, cp, pp,
+                                                    (PACK_FLUSH if flush else 0) | (PACK_GAPLESS if gapless else 0), ip,
+                                                    ctypes.c_void_p(stream) if stream else None))
+        return blocks, counts, peak, infos
+
+    def integrated_lufs(self, blocks, counts, lufs=None, stream=None):
+        """Gated integrated loudness of every row of blocks float32
+        [n, stride] holding counts[s] block energies, on the GPU
+        (mp3d_batch_loudness_integrated); host arrays or device tensors.
+        Returns lufs float32 [n], -inf for a row of fewer than 4 blocks."""
+        n, stride = int(blocks.shape[0]), int(blocks.shape[1])
+        if not hasattr(counts, "data_ptr"):
+            counts = np.ascontiguousarray(counts, np.int32)
+        if lufs is None:
+            lufs = np.zeros(n, np.float32)
+        bp, k1 = _ptr(blocks)
+        cp, k2 = _ptr(counts)
+        lp, k3 = _ptr(lufs)
+        self._ck(self._L.mp3d_batch_loudness_integrated(self._h, bp if stride else None, stride, cp, n, lp,
+                                                        ctypes.c_void_p(stream) if stream else None))
+        return lufs
+
+    def loudness_time_us(self):
+        """Device-side microseconds of the loudness stage of the last
+        loudness call (after set_timing)."""
+        t = ctypes.c_float()
+        self._ck(self._L.mp3d_batch_loudness_time(self._h, ctypes.byref(t)))
         return float(t.value)
 
     @staticmethod
@@ -668,6 +774,30 @@ def feat_max_frames(frames, min_in_hz=8000):
     """Smallest stride of decode_features that can never overflow for streams
     of input rate >= min_in_hz (mp3d_feat_max_frames)."""
     return int(_check(lib().mp3d_feat_max_frames(int(frames), int(min_in_hz))))
+
+
+def loudness_filter(hz):
+    """The loudness sink's K-weighting at rate hz (mp3d_loudness_filter; no
+    GPU needed): float64 [2, 5], b0 b1 b2 a1 a2 of the shelf and the high-pass."""
+    c = np.zeros(10, np.float64)
+    _check(lib().mp3d_loudness_filter(int(hz), c.ctypes.data, c.size))
+    return c.reshape(2, 5)
+
+
+def loud_max_blocks(hz, frames, min_in_hz=8000):
+    """Smallest stride of decode_loudness that can never overflow for streams
+    of input rate >= min_in_hz (mp3d_loud_max_blocks)."""
+    return int(_check(lib().mp3d_loud_max_blocks(int(hz), int(frames), int(min_in_hz))))
+
+
+def integrated_lufs(z):
+    """Gated integrated loudness (BS.1770-4) of a sequence of 100 ms block
+    energies (mp3d_loudness_integrated; no GPU needed): float, -inf when
+    fewer than 4 blocks or none passes the gates."""
+    z = np.ascontiguousarray(z, np.float32).reshape(-1)
+    out = ctypes.c_double()
+    _check(lib().mp3d_loudness_integrated(z.ctypes.data if z.size else None, z.size, ctypes.byref(out)))
+    return float(out.value)
 
 
 def long_packed_bound(data, out_hz):

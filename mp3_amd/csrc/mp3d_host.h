@@ -1,6 +1,7 @@
 /*
  * mp3d_host.h -- private to the host sources (mp3d_host_tables.cpp,
- * mp3d_batch.cpp, mp3d_long.cpp, mp3d_dec.cpp, mp3d_sinks.cpp): the error
+ * mp3d_batch.cpp, mp3d_long.cpp, mp3d_dec.cpp, mp3d_sinks.cpp,
+ * mp3d_loudness.cpp): the error
  * macro, the owning device buffer, the batch handle and the internal
  * functions that cross those files.  Nothing here is exported (the library
  * is built with hidden visibility; the C ABI is include/mp3d.h).
@@ -24,6 +25,7 @@
 #include "mp3d_hostparse.h"
 #include "mp3d_resample.h"
 #include "mp3d_features.h"
+#include "mp3d_loudness.h"
 #include "mp3d_launch.h"
 
 namespace mp3d {
@@ -225,6 +227,28 @@ struct mp3d_batch {
             tm.timed = false;
         }
     } ft;
+    /* loudness sink (mp3d_batch_set_loudness; mp3d_loudness.h): on = false is
+     * off, and then none of these buffers exists.  st, plan, cin, cnt, pk, lu
+     * (integrated loudness of a call's rows) and endst hold max_streams
+     * entries; smp, out (staging for a host sink) and the per-tile scratch
+     * tz, entry, part, tpeak grow with the calls. */
+    struct LoudnessSink {
+        bool on = false;
+        int H = 0;
+        mp3d::DevBuf<LdTab> tab;
+        mp3d::DevBuf<LdState> st;
+        mp3d::DevBuf<LdPlan> plan;
+        mp3d::DevBuf<int32_t> cin, cnt;
+        mp3d::DevBuf<float> smp, out, pk, lu, tpeak;
+        mp3d::DevBuf<double> tz, entry, part, endst;
+        mp3d::StageTimer tm;
+        void off() {
+            tab.release(), st.release(), plan.release(), cin.release(), cnt.release(), smp.release(), out.release();
+            pk.release(), lu.release(), tpeak.release(), tz.release(), entry.release(), part.release(), endst.release();
+            on = false, H = 0;
+            tm.timed = false;
+        }
+    } ld;
 };
 
 namespace mp3d {
@@ -320,6 +344,15 @@ void rs_sizes(int in_hz, int out_hz, int *L, int *M, int *T);
 /* the most outputs one call of `frames` frames at in_hz can emit: all its
  * inputs plus a pending tail of `post` inputs, ceil((N + post) L / M) */
 long long rs_bound(int in_hz, int out_hz, long long frames);
+/* The tail of a sink call on stream s: n streams' rows (`unit` bytes each)
+ * and counts reach the caller.  drows [n][dstride] and dcnt [n] are where
+ * the kernels put them: the caller's own memory when rows_dev / cnt_dev
+ * (nothing to do for that part), else the handle's staging, and then only
+ * each stream's own rows are copied to the caller's rows [n][stride].
+ * Returns after the work is queued when both are device memory, else when
+ * it is done. */
+int deliver_rows(hipStream_t s, int n, size_t unit, const void *drows, long long dstride, void *rows, long long stride,
+                 const int32_t *dcnt, int *count, bool rows_dev, bool cnt_dev);
 
 } // namespace mp3d
 

@@ -10,10 +10,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-/* (layouts: mp3d_internal.h, mp3d_resample.h, mp3d_features.h) */
+/* (layouts: mp3d_internal.h, mp3d_resample.h, mp3d_features.h, mp3d_loudness.h) */
 struct StreamState; struct FrameRec; struct UnitMeta; struct DevTables;
 struct RsState; struct RsCfg; struct RsPlan; struct RsLong;
 struct FtState; struct FtPlan; struct FtTab;
+struct LdState; struct LdPlan; struct LdTab;
 
 namespace mp3d {
 
@@ -81,6 +82,16 @@ void launch_resample_long(const float *rows, const void *infos, const int *a, co
 void launch_features(const float *samples, const int32_t *counts, FtState *st, FtPlan *plan, const FtTab *tab, float *feat,
                      int32_t *feat_count, int n, long long sample_stride, long long feat_stride, int tiles, int flush,
                      hipStream_t strm);
+
+/* ---- mp3d_loudness.hip ---- */
+/* k_ld_plan + k_ld_local + k_ld_carry + k_ld_energy + k_ld_finish: packed float32 samples to 100 ms block energies */
+void launch_loudness(const float *samples, const int32_t *counts, LdState *st, LdPlan *plan, const LdTab *tab, int H,
+                     int ch, double *tz, double *entry, double *part, float *tpeak, double *endst, float *blocks,
+                     int32_t *block_count, float *peak, int n, long long sample_stride, long long block_stride,
+                     int tiles, int flush, hipStream_t strm);
+/* k_ld_gate: rows of block energies to gated integrated loudness */
+void launch_loudness_gate(const float *blocks, long long block_stride, const int32_t *counts, float *lufs, int n,
+                          hipStream_t strm);
 
 } // namespace mp3d
 

@@ -159,6 +159,7 @@ extern "C" int mp3d_batch_set_output(mp3d_batch *b, int out_hz, int out_channels
     if (r) return r;
     HIPCHK(hipStreamSynchronize(b->own));
     b->ft.off(); /* the feature sink reads this sink's format: off with any change of it */
+    b->ld.off(); /* and so does the loudness sink */
     mp3d_batch::PackedSink &k = b->rs;
     if (out_hz == 0) {
         k.off();
@@ -177,15 +178,8 @@ extern "C" int mp3d_batch_set_output(mp3d_batch *b, int out_hz, int out_channels
     return r;
 }
 
-/* The tail of a sink call on stream s: n streams' rows (`unit` bytes each)
- * and counts reach the caller.  drows [n][dstride] and dcnt [n] are where
- * the kernels put them: the caller's own memory when rows_dev / cnt_dev
- * (nothing to do for that part), else the handle's staging, and then only
- * each stream's own rows are copied to the caller's rows [n][stride].
- * Returns after the work is queued when both are device memory, else when
- * it is done. */
-static int deliver_rows(hipStream_t s, int n, size_t unit, const void *drows, long long dstride, void *rows,
-                        long long stride, const int32_t *dcnt, int *count, bool rows_dev, bool cnt_dev) {
+int mp3d::deliver_rows(hipStream_t s, int n, size_t unit, const void *drows, long long dstride, void *rows,
+                       long long stride, const int32_t *dcnt, int *count, bool rows_dev, bool cnt_dev) {
     if (rows_dev && cnt_dev) return MP3D_OK;
     std::vector<int32_t> hc((size_t)n);
     HIPCHK(hipMemcpyAsync(hc.data(), dcnt, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
@@ -278,6 +272,7 @@ extern "C" int mp3d_batch_set_window(mp3d_batch *b, int first, int n, const long
     /* a window restart: the slots' resamplers and fed counts restart with it */
     HIPCHK(hipMemsetAsync(b->rs.st + first, 0, sizeof(RsState) * (size_t)n, s));
     if (b->ft.st) HIPCHK(hipMemsetAsync(b->ft.st + first, 0, sizeof(FtState) * (size_t)n, s));
+    if (b->ld.st) HIPCHK(hipMemsetAsync(b->ld.st + first, 0, sizeof(LdState) * (size_t)n, s));
     if (lo)
         HIPCHK(hipMemcpy2DAsync(b->rs.st + first, sizeof(RsState), w.data(), sizeof(RsWindow), sizeof(RsWindow), (size_t)n,
                                 hipMemcpyHostToDevice, s));
