@@ -621,6 +621,114 @@ MP3D_API int mp3d_batch_loudness_integrated(mp3d_batch *b, const float *blocks, 
  * needs mp3d_batch_set_timing */
 MP3D_API int mp3d_batch_loudness_time(mp3d_batch *b, float *us);
 
+/* ---- true peak and gain (normalising on the GPU) ---------------------------- *
+ * Input signal of a stream: its packed-sink output in the handle's format
+ * (any of the nine rates, out_channels 1 or 2, float32 interleaved):
+ * x_c[0 .. N) since the stream's last true-peak restart.
+ *
+ * Oversampling: R = 4 at every rate, T = 12 taps per phase; the filter is
+ * defined by formula (BS.1770's Annex 2 table is not used):
+ *   p = 0:     taps[0][5] = 1, every other taps[0][j] = 0   (by definition)
+ *   p = 1..3:  t = p/4 - (j - 5),  j = 0 .. 11
+ *              w = I0(6 sqrt(1 - (t/6)^2)) / I0(6) for |t| < 6, else 0
+ *                                                        (Kaiser, beta 6)
+ *              h = sinc(t) w;  taps[p][j] = h / sum_j h
+ * computed in double, rounded to float32 (mp3d_truepeak_filter).
+ *   u_c[4n + p] = sum_j taps[p][j] x_c[n - 5 + j],  x outside [0, N) = 0
+ * Each u is ONE float32 fmaf chain in ascending j, starting from 0, so its
+ * bits do not depend on which call, tile or thread computes it.  Phase 0
+ * reproduces x exactly (the kernel takes |x|), so a flushed stream's true
+ * peak is never below its sample peak.
+ *
+ * Emit rule: index n (its four values, all channels) is emitted once sample
+ * n + 6 has been seen, so after N samples the indices n < max(N - 6, 0) have
+ * been emitted.  MP3D_PACK_FLUSH also emits every n < N, with zeros past N,
+ * then restarts the stream's true-peak state.
+ *
+ * tpeak[s] of a call = max |u_c[4n + p]| over c, p and the indices n the call
+ * emits, float32; 0 when it emits none.  A maximum is exact: the maximum of
+ * tpeak[s] over ANY split of a stream into calls equals the one-call value
+ * bit for bit, and a caller folds the calls of a stream with max.
+ *
+ * Numerical contract: against the definition evaluated in float64 with the
+ * float32 taps, with P the largest |x| of the stream since its restart,
+ *   |tpeak - ref| <= 23 * 2^-24 * P
+ * (12 roundings of a chain whose sum of |taps| is at most 1.856).
+ *
+ * The per-stream true-peak state (a sample count and the last 11 samples of
+ * each channel) lives in the handle while true peak is set, not in the state
+ * blob.  It restarts where the loudness state does: at create, at
+ * mp3d_batch_reset, at mp3d_batch_set_state on its slot, at
+ * mp3d_batch_set_output (which also turns true peak off), at
+ * mp3d_batch_set_true_peak, at mp3d_batch_set_window on its slot and after
+ * its own flush.  Features, loudness and true peak may all be on.
+ *
+ * Gain rule (mp3d_batch_normalize_gain), in double, rounded to float32:
+ *   g = 10^((target_lufs - lufs[s]) / 20)
+ *   if tpeak[s] > 0 and g * tpeak[s] > c, c = 10^(max_dbtp / 20):
+ *       g = c / tpeak[s]
+ *   lufs[s] not finite (-inf: under 400 ms or silent; NaN): g = 1 exactly,
+ *   untouched by the limit.
+ *
+ * Apply (mp3d_batch_apply_gain): out[s][i][c] = samples[s][i][c] * gain[s],
+ * one float32 multiply, for i < counts[s]; nothing past that is written.
+ * int16 output is the packed sink's conversion of that product,
+ * clamp(floor(y * 32768 + 0.5)); float32 is not clipped.                     */
+
+/* host only, no GPU: taps[4][12] as defined above (NULL: size only); cap =
+ * floats taps can hold; returns 48, or MP3D_E_ARG for a short cap */
+MP3D_API long long mp3d_truepeak_filter(float *taps, size_t cap);
+
+/* Needs a packed format (mp3d_batch_set_output), else MP3D_E_ARG.  on != 0
+ * uploads the taps, restarts every slot's true-peak state and waits for the
+ * handle's work; on = 0 turns the tap off and frees its buffers. */
+MP3D_API int mp3d_batch_set_true_peak(mp3d_batch *b, int on);
+
+/* The tap: feeds counts[s] (clamped to [0, sample_stride]) sample frames from
+ * samples + s * sample_stride * out_channels per stream through the slots'
+ * true-peak state and writes tpeak[s].  samples, counts and tpeak are host or
+ * device memory (a host samples array is read whole); the call is
+ * asynchronous when all three are device memory.  Device pointers must be
+ * float-aligned, else MP3D_E_ARG; sample_stride is at most 2^31 - 1 - 4096.
+ * flags: MP3D_PACK_FLUSH only.  Runs on the device out and out_count of
+ * mp3d_batch_decode_packed (float32), or with n_streams = 1 on the device
+ * output of mp3d_batch_decode_long_packed, whose one stream is spread over
+ * the whole GPU.  Leaves decoder, resampler, feature and loudness state
+ * untouched.  MP3D_E_ARG before mp3d_batch_set_true_peak.                   */
+MP3D_API int mp3d_batch_true_peak(mp3d_batch *b, const float *samples, long long sample_stride, const int *counts,
+                                  int n_streams, float *tpeak, int flags, void *hip_stream);
+
+/* Exactly mp3d_batch_decode_loudness, then the true-peak tap on the same
+ * handle-owned samples and counts before returning: blocks, block_count, peak
+ * as there, tpeak as above.  flags: MP3D_PACK_FLUSH | MP3D_PACK_GAPLESS (the
+ * flush ends resampler, loudness and true peak).  Needs both
+ * mp3d_batch_set_loudness and mp3d_batch_set_true_peak, else MP3D_E_ARG.    */
+MP3D_API int mp3d_batch_decode_measure(mp3d_batch *b, const uint8_t *frames, const uint64_t *offsets,
+                                       const uint32_t *sizes, int n_streams, int frames_per_stream, float *blocks,
+                                       long long block_stride, int *block_count, float *peak, float *tpeak, int flags,
+                                       mp3d_frame_info *infos, void *hip_stream);
+
+/* The gain rule above for n_streams streams: lufs, tpeak (NULL: no limit) and
+ * gain are host or device memory (device pointers float-aligned); the call is
+ * asynchronous when all are device memory.  Needs no sink.                 */
+MP3D_API int mp3d_batch_normalize_gain(mp3d_batch *b, const float *lufs, const float *tpeak, int n_streams,
+                                       double target_lufs, double max_dbtp, float *gain, void *hip_stream);
+
+/* Applies gain[s] to counts[s] (clamped to [0, sample_stride]; < 0 writes
+ * nothing) sample frames of every stream: samples as for the tap, out
+ * float32 (f32 != 0) or int16 with the same stride, host or device memory.  A
+ * device out must be aligned to one sample frame (as
+ * mp3d_batch_decode_packed's out); a host out is filled by one copy per
+ * stream.  out == samples (in place) is allowed for float32.  Needs a packed
+ * format, for the channel count, else MP3D_E_ARG.                           */
+MP3D_API int mp3d_batch_apply_gain(mp3d_batch *b, const float *samples, long long sample_stride, const int *counts,
+                                   int n_streams, const float *gain, void *out, int f32, void *hip_stream);
+
+/* device-side microseconds of the true-peak stage of the last true-peak call
+ * (mp3d_batch_true_peak, mp3d_batch_decode_measure); needs
+ * mp3d_batch_set_timing */
+MP3D_API int mp3d_batch_true_peak_time(mp3d_batch *b, float *us);
+
 /* ---- diagnostics -------------------------------------------------------- */
 MP3D_API const char *mp3d_strerror(int err);
 MP3D_API int mp3d_last_hip_error(void);

@@ -58,7 +58,9 @@ EXPORTS = ["mp3d_dec_create", "mp3d_dec_create_on", "mp3d_dec_destroy", "mp3d_de
            "mp3d_batch_decode_features", "mp3d_batch_features", "mp3d_batch_feature_time", "mp3d_batch_set_window",
            "mp3d_batch_sink_window", "mp3d_loudness_filter", "mp3d_loud_max_blocks", "mp3d_batch_set_loudness",
            "mp3d_batch_loudness", "mp3d_batch_decode_loudness", "mp3d_loudness_integrated",
-           "mp3d_batch_loudness_integrated", "mp3d_batch_loudness_time"]
+           "mp3d_batch_loudness_integrated", "mp3d_batch_loudness_time", "mp3d_truepeak_filter",
+           "mp3d_batch_set_true_peak", "mp3d_batch_true_peak", "mp3d_batch_decode_measure",
+           "mp3d_batch_normalize_gain", "mp3d_batch_apply_gain", "mp3d_batch_true_peak_time"]
 
 OPT_CRC_CHECK = 1  # MP3D_OPT_CRC_CHECK: drop frames whose CRC-16 mismatches
 LONG_GAPLESS = 1  # MP3D_LONG_GAPLESS: apply the LAME tag's trim inside decode_long_packed
@@ -149,6 +151,15 @@ def _bind(L):
         L.mp3d_loudness_integrated.argtypes = [vp, ctypes.c_longlong, ctypes.POINTER(ctypes.c_double)]
         L.mp3d_batch_loudness_integrated.argtypes = [vp, vp, ctypes.c_longlong, vp, i, vp, vp]
         L.mp3d_batch_loudness_time.argtypes = [vp, vp]
+    if hasattr(L, "mp3d_batch_set_true_peak"):  # (an older build loaded for an A/B lacks true peak and gain)
+        L.mp3d_truepeak_filter.argtypes = [vp, ctypes.c_size_t]
+        L.mp3d_truepeak_filter.restype = ctypes.c_longlong
+        L.mp3d_batch_set_true_peak.argtypes = [vp, i]
+        L.mp3d_batch_true_peak.argtypes = [vp, vp, ctypes.c_longlong, vp, i, vp, i, vp]
+        L.mp3d_batch_decode_measure.argtypes = [vp, vp, u64p, u32p, i, i, vp, ctypes.c_longlong, vp, vp, vp, i, vp, vp]
+        L.mp3d_batch_normalize_gain.argtypes = [vp, vp, vp, i, ctypes.c_double, ctypes.c_double, vp, vp]
+        L.mp3d_batch_apply_gain.argtypes = [vp, vp, ctypes.c_longlong, vp, i, vp, vp, i, vp]
+        L.mp3d_batch_true_peak_time.argtypes = [vp, vp]
     if hasattr(L, "mp3d_debug_wglds_probe"):  # libmp3d_wglds.so only (tests/test_gpu_wglds.py)
         L.mp3d_debug_wglds_probe.argtypes = [i, i, vp, i]
     return L
@@ -369,6 +380,7 @@ class BatchDecoder:
         self._out = (int(hz), int(channels))
         self._mels = 0  # a change of the output format turns the feature sink off
         self._loud = False  # and the loudness sink
+        self._tp = False  # and the true-peak tap
 
     def decode_packed(self, frames, offsets, sizes, frames_per_stream, out=None, counts=None, infos=None, f32=True,
                       flush=False, stride=None, stream=None, gapless=False):
@@ -610,6 +622,146 @@ class BatchDecoder:
         self._ck(self._L.mp3d_batch_loudness_time(self._h, ctypes.byref(t)))
         return float(t.value)
 
+    def set_true_peak(self, on=True):
+        """Turn the true-peak tap on or off (mp3d_batch_set_true_peak): the
+        4x oversampled peak of the packed output, whatever its format.  Needs
+        set_output.  Restarts every stream's true-peak state."""
+        self._ck(self._L.mp3d_batch_set_true_peak(self._h, int(bool(on))))
+        self._tp = bool(on)
+
+    def true_peak(self, samples, counts, tpeak=None, flush=False, stride=None, stream=None):
+        """The true-peak tap (mp3d_batch_true_peak): samples float32
+        [n, sample_stride, channels] in the packed format, counts int32 [n]
+        sample frames per stream (both host arrays or device tensors), e.g.
+        the device out and counts of decode_packed; stride: the sample stride
+        when it is not samples.shape[1].  tpeak: None (allocate host) or
+        float32 array/tensor [n].  flush=True emits the last 6 indices of every
+        stream and restarts it.  Returns tpeak; the true peak of a stream fed
+        in several calls is the max of theirs."""
+        n, ss = int(samples.shape[0]), int(samples.shape[1]) if stride is None else int(stride)
+        if not hasattr(counts, "data_ptr"):
+            counts = np.ascontiguousarray(counts, np.int32)
+        if tpeak is None:
+            tpeak = np.zeros(n, np.float32)
+        sp, k1 = _ptr(samples)
+        cp, k2 = _ptr(counts)
+        tp, k3 = _ptr(tpeak)
+        self._ck(self._L.mp3d_batch_true_peak(self._h, sp if ss else None, ss, cp, n, tp, PACK_FLUSH if flush else 0,
+                                              ctypes.c_void_p(stream) if stream else None))
+        return tpeak
+
+    def decode_measure(self, frames, offsets, sizes, frames_per_stream, blocks=None, counts=None, peak=None,
+                       tpeak=None, infos=None, flush=False, stride=None, stream=None, gapless=False):
+        """decode_loudness plus the true-peak tap on the same samples
+        (mp3d_batch_decode_measure); needs set_loudness and set_true_peak.
+        Returns (blocks, counts, peak, tpeak, infos)."""
+        off, sz = self._geom(offsets, sizes)
+        n, F = off.size, int(frames_per_stream)
+        hz = getattr(self, "_out", (0, 0))[0]
+        blocks, counts, peak, stride = self._loud_args(n, blocks, counts, peak, stride, lambda: loud_max_blocks(hz, F))
+        if tpeak is None:
+            tpeak = np.zeros(n, np.float32)
+        if infos is None:
+            infos = np.zeros((n, F), FRAME_INFO_DT)
+        fp, k1 = _ptr(frames)
+        op, k2 = _ptr(blocks)
+        cp, k3 = _ptr(counts)
+        pp, k4 = _ptr(peak)
+        tp, k5 = _ptr(tpeak)
+        ip, k6 = _ptr(infos)
+        self._ck(self._L.mp3d_batch_decode_measure(self._h, fp, off.ctypes.data, sz.ctypes.data, n, F, op, stride, cp, pp,
+                                                   tp, (PACK_FLUSH if flush else 0) | (PACK_GAPLESS if gapless else 0),
+                                                   ip, ctypes.c_void_p(stream) if stream else None))
+        return blocks, counts, peak, tpeak, infos
+
+    def normalize_gain(self, lufs, tpeak=None, target=-23.0, max_dbtp=-1.0, gain=None, stream=None):
+        """The gain that brings each stream from lufs[s] to target LUFS,
+        limited so that gain * tpeak[s] stays at or below max_dbtp dBTP
+        (mp3d_batch_normalize_gain); tpeak=None: no limit.  A stream whose
+        loudness is not finite gets gain 1.  Host arrays or device tensors,
+        float32 [n].  Returns gain."""
+        if not hasattr(lufs, "data_ptr"):
+            lufs = np.ascontiguousarray(lufs, np.float32)
+        if tpeak is not None and not hasattr(tpeak, "data_ptr"):
+            tpeak = np.ascontiguousarray(tpeak, np.float32)
+        n = int(lufs.shape[0])
+        if gain is None:
+            gain = np.zeros(n, np.float32)
+        lp, k1 = _ptr(lufs)
+        tp, k2 = _ptr(tpeak)
+        gp, k3 = _ptr(gain)
+        self._ck(self._L.mp3d_batch_normalize_gain(self._h, lp, tp, n, float(target), float(max_dbtp), gp,
+                                                   ctypes.c_void_p(stream) if stream else None))
+        return gain
+
+    def apply_gain(self, samples, counts, gain, out=None, f32=True, stream=None):
+        """out[s, i, c] = samples[s, i, c] * gain[s] for i < counts[s]
+        (mp3d_batch_apply_gain): samples float32 [n, stride, channels] in the
+        packed format, counts int32 [n], gain float32 [n]; out: None (allocate
+        host, zeros past the counts) or float32 (int16 with f32=False)
+        array/tensor of samples' shape, which may be samples itself for
+        float32.  Nothing past counts[s] is written.  Returns out."""
+        n, ss = int(samples.shape[0]), int(samples.shape[1])
+        if not hasattr(counts, "data_ptr"):
+            counts = np.ascontiguousarray(counts, np.int32)
+        if not hasattr(gain, "data_ptr"):
+            gain = np.ascontiguousarray(gain, np.float32)
+        if out is None:
+            out = np.zeros(tuple(samples.shape), np.float32 if f32 else np.int16)
+        sp, k1 = _ptr(samples)
+        cp, k2 = _ptr(counts)
+        gp, k3 = _ptr(gain)
+        op, k4 = _ptr(out)
+        self._ck(self._L.mp3d_batch_apply_gain(self._h, sp if ss else None, ss, cp, n, gp, op, int(bool(f32)),
+                                               ctypes.c_void_p(stream) if stream else None))
+        return out
+
+    def true_peak_time_us(self):
+        """Device-side microseconds of the true-peak stage of the last
+        true-peak call (after set_timing)."""
+        t = ctypes.c_float()
+        self._ck(self._L.mp3d_batch_true_peak_time(self._h, ctypes.byref(t)))
+        return float(t.value)
+
+    def decode_normalized(self, frames, offsets, sizes, frames_per_stream, target=-23.0, max_dbtp=-1.0, out=None,
+                          f32=True, gapless=False):
+        """Decode streams that are whole in this call and normalise them to
+        target LUFS under max_dbtp dBTP, all on the device with no host sync
+        between the stages: decode_packed(flush), loudness(flush),
+        true_peak(flush), integrated_lufs, normalize_gain, apply_gain.  Needs
+        set_loudness and set_true_peak.  out: None (allocate host) or float32
+        (int16 with f32=False) array/tensor [n, packed_max_samples, channels].
+        Returns (out, counts, lufs, tpeak, gain, infos): out as given, the rest
+        host arrays."""
+        import torch
+        if not (getattr(self, "_loud", False) and getattr(self, "_tp", False)):
+            raise MP3DError("decode_normalized needs set_loudness and set_true_peak")
+        off, sz = self._geom(offsets, sizes)
+        n, F = off.size, int(frames_per_stream)
+        hz, ch = self._out
+        S = packed_max_samples(hz, F)
+        if out is None:
+            out = np.zeros((n, S, ch), np.float32 if f32 else np.int16)
+        if tuple(out.shape) != (n, S, ch):
+            raise ValueError("out must be [%d, %d, %d]" % (n, S, ch))
+        dev = torch.device("cuda", self.device)
+        smp = torch.empty((n, S, ch), dtype=torch.float32, device=dev)
+        counts, bc = (torch.empty((n,), dtype=torch.int32, device=dev) for _ in range(2))
+        nb = max((S + (hz + 5) // 10 - 1) // ((hz + 5) // 10), 1)
+        blocks = torch.empty((n, nb), dtype=torch.float32, device=dev)
+        peak, tpeak, lufs, gain = (torch.empty((n,), dtype=torch.float32, device=dev) for _ in range(4))
+        infos = torch.empty((n, F, 6), dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)  # (nothing of the allocator's is on the handle's stream)
+        self.decode_packed(frames, off, sz, F, out=smp, counts=counts, infos=infos, flush=True, gapless=gapless)
+        self.loudness(smp, counts, blocks=blocks, block_counts=bc, peak=peak, flush=True)
+        self.true_peak(smp, counts, tpeak=tpeak, flush=True)
+        self.integrated_lufs(blocks, bc, lufs=lufs)
+        self.normalize_gain(lufs, tpeak, target=target, max_dbtp=max_dbtp, gain=gain)
+        self.apply_gain(smp, counts, gain, out=out, f32=f32)
+        self.sync()
+        infos = infos.cpu().numpy().view(FRAME_INFO_DT).reshape(n, F)
+        return out, counts.cpu().numpy(), lufs.cpu().numpy(), tpeak.cpu().numpy(), gain.cpu().numpy(), infos
+
     @staticmethod
     def _nbytes(x):
         """Byte size of a contiguous host array / device tensor (its element
@@ -798,6 +950,14 @@ def integrated_lufs(z):
     out = ctypes.c_double()
     _check(lib().mp3d_loudness_integrated(z.ctypes.data if z.size else None, z.size, ctypes.byref(out)))
     return float(out.value)
+
+
+def truepeak_filter():
+    """The true-peak tap's 4x oversampling filter (mp3d_truepeak_filter; no
+    GPU needed): float32 [4, 12], row p the taps of phase p."""
+    t = np.zeros((4, 12), np.float32)
+    _check(lib().mp3d_truepeak_filter(t.ctypes.data, t.size))
+    return t
 
 
 def long_packed_bound(data, out_hz):

@@ -39,6 +39,17 @@ __device__ __forceinline__ void wave_sync() { __asm__ volatile("" ::: "memory");
 
 __device__ __forceinline__ uint32_t bswap32(uint32_t x) { return __builtin_bswap32(x); }
 
+/* The library's int16 rounding of a float32 sample, wherever packed PCM is
+ * stored as int16 (mp3d_resample.hip rs_store, mp3d_normalize.hip
+ * k_gain_apply): clamp(floor(y * 32768 + 0.5)) of the exact product
+ * (v + 0.5f itself could round up across an integer): the scaling and
+ * v - floor(v) are exact */
+__device__ __forceinline__ short pcm_i16(float y) {
+    const float v = y * 32768.0f, fl = floorf(v);
+    const float r = v - fl >= 0.5f ? fl + 1.0f : fl;
+    return (short)fminf(fmaxf(r, -32768.0f), 32767.0f);
+}
+
 /* MP3D_LDS_ENTRY(): the first statement of every kernel (tests/
  * test_wglds_coverage.py), nothing in the product build.  In the debug build
  * libmp3d_wglds.so (-DMP3D_WG_LDS_POISON, mp3_amd/_build.py) every workgroup

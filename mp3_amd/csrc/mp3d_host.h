@@ -1,7 +1,7 @@
 /*
  * mp3d_host.h -- private to the host sources (mp3d_host_tables.cpp,
  * mp3d_batch.cpp, mp3d_long.cpp, mp3d_dec.cpp, mp3d_sinks.cpp,
- * mp3d_loudness.cpp): the error
+ * mp3d_loudness.cpp, mp3d_normalize.cpp): the error
  * macro, the owning device buffer, the batch handle and the internal
  * functions that cross those files.  Nothing here is exported (the library
  * is built with hidden visibility; the C ABI is include/mp3d.h).
@@ -26,6 +26,7 @@
 #include "mp3d_resample.h"
 #include "mp3d_features.h"
 #include "mp3d_loudness.h"
+#include "mp3d_normalize.h"
 #include "mp3d_launch.h"
 
 namespace mp3d {
@@ -249,6 +250,34 @@ struct mp3d_batch {
             tm.timed = false;
         }
     } ld;
+    /* true-peak tap and gain (mp3d_batch_set_true_peak; mp3d_normalize.h):
+     * on = false is off, and then taps, st and plan do not exist.  st, plan,
+     * cin, tp hold max_streams entries; smp (a host caller's samples) and the
+     * per-tile scratch tile grow with the calls.  The gain calls need only a
+     * packed format: their staging (lu, gtp, gain for host arrays of the gain
+     * rule; ccnt, gsmp, gcin, gg, out of mp3d_batch_apply_gain) is made by the
+     * first call that needs it and freed with the packed format. */
+    struct NormalizeSink {
+        bool on = false;
+        mp3d::DevBuf<float> taps;
+        mp3d::DevBuf<TpState> st;
+        mp3d::DevBuf<TpPlan> plan;
+        mp3d::DevBuf<int32_t> cin, ccnt, gcin;
+        mp3d::DevBuf<float> smp, tile, tp, lu, gtp, gain, gsmp, gg;
+        mp3d::DevBuf<void> out;
+        mp3d::StageTimer tm;
+        /* the tap: the gain calls' staging stays */
+        void tap_off() {
+            taps.release(), st.release(), plan.release(), cin.release(), smp.release(), tile.release(), tp.release();
+            on = false;
+            tm.timed = false;
+        }
+        void off() {
+            tap_off();
+            ccnt.release(), gcin.release(), lu.release(), gtp.release(), gain.release(), gsmp.release(), gg.release();
+            out.release();
+        }
+    } nm;
 };
 
 namespace mp3d {

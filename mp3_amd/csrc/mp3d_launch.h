@@ -10,11 +10,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-/* (layouts: mp3d_internal.h, mp3d_resample.h, mp3d_features.h, mp3d_loudness.h) */
+/* (layouts: mp3d_internal.h, mp3d_resample.h, mp3d_features.h, mp3d_loudness.h, mp3d_normalize.h) */
 struct StreamState; struct FrameRec; struct UnitMeta; struct DevTables;
 struct RsState; struct RsCfg; struct RsPlan; struct RsLong;
 struct FtState; struct FtPlan; struct FtTab;
 struct LdState; struct LdPlan; struct LdTab;
+struct TpState; struct TpPlan;
 
 namespace mp3d {
 
@@ -92,6 +93,18 @@ void launch_loudness(const float *samples, const int32_t *counts, LdState *st, L
 /* k_ld_gate: rows of block energies to gated integrated loudness */
 void launch_loudness_gate(const float *blocks, long long block_stride, const int32_t *counts, float *lufs, int n,
                           hipStream_t strm);
+
+/* ---- mp3d_normalize.hip ---- */
+/* k_tp_plan + k_tp_peak + k_tp_finish: packed float32 samples to the 4x oversampled peak of each stream */
+void launch_true_peak(const float *samples, const int32_t *counts, TpState *st, TpPlan *plan, const float *taps,
+                      float *tilepk, float *tpeak, int n, long long sample_stride, int ch, int tiles, int flush,
+                      hipStream_t strm);
+/* k_gain_calc: loudness and true peak (or null) to the normalisation gain; c = 10^(max_dbtp / 20) */
+void launch_gain_calc(const float *lufs, const float *tpeak, float *gain, int n, double target, double c,
+                      hipStream_t strm);
+/* k_gain_apply: packed float32 samples times their stream's gain, as float32 or int16; ccnt: the clamped counts */
+void launch_gain_apply(const float *samples, const int32_t *counts, const float *gain, void *out, int32_t *ccnt,
+                       bool f32, int ch, int n, long long sample_stride, int chunks, hipStream_t strm);
 
 } // namespace mp3d
 

@@ -168,16 +168,9 @@ __device__ __forceinline__ void rs_store(void *__restrict__ out, size_t at, cons
         if (OC == 2) *(float2 *)((float *)out + at) = make_float2(acc[0], acc[1]);
         else ((float *)out)[at] = acc[0];
     } else {
-        /* the library's int16 rounding: clamp(floor(y * 32768 + 0.5)) of the
-         * exact sum (v + 0.5f itself could round up across an integer): the
-         * scaling and v - floor(v) are exact */
-        short q[OC];
+        short q[OC]; /* (the library's int16 rounding: mp3d_device.h) */
 #pragma unroll
-        for (int c = 0; c < OC; c++) {
-            const float v = acc[c] * 32768.0f, fl = floorf(v);
-            const float r = v - fl >= 0.5f ? fl + 1.0f : fl;
-            q[c] = (short)fminf(fmaxf(r, -32768.0f), 32767.0f);
-        }
+        for (int c = 0; c < OC; c++) q[c] = pcm_i16(acc[c]);
         if (OC == 2) *(short2 *)((short *)out + at) = make_short2(q[0], q[1]);
         else ((short *)out)[at] = q[0];
     }
