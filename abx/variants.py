@@ -491,8 +491,12 @@ VARS["NTL"] = [("                            if (i + 4 * k < len) v[k] = *(const
 VARS["NTS"] = [("                        *(uint4 *)(row + k) = make_uint4(wv[0], wv[1], wv[2], wv[3]);",
                 "                        { typedef uint32_t u4v __attribute__((ext_vector_type(4))); __builtin_nontemporal_store((u4v){wv[0], wv[1], wv[2], wv[3]}, (u4v *)(row + k)); }")]
 # k_huffman waves per CU (open is[] rows per CU = 64 x waves)
-VARS["HW12"] = [("#define HUFF_WAVES 16", "#define HUFF_WAVES 12")]
+VARS["HW12"] = [("#define HUFF_WAVES 16", "#define HUFF_WAVES 12")]  # (round 5 sources)
 VARS["HW8"] = [("#define HUFF_WAVES 16", "#define HUFF_WAVES 8")]
+# round 7: k_huffman waves per CU x big_values groups per store burst (the staging area follows the
+# wave count): HwBb.  H12B8 is the product; H16B4 spills (24 VGPRs).  profiles/r07_huff_bursts.txt
+for _w, _b in ((16, 2), (16, 4), (12, 2), (12, 4), (12, 8)):
+    VARS["H%dB%d" % (_w, _b)] = [("FLAGS", "-DHUFF_WAVES=%d" % _w), ("FLAGS", "-DHUFF_BURST=%d" % _b)]
 # k_rank segment size (units ranked together): 1 024 / 2 048 instead of 4 096
 VARS["RK1"] = [("#define RANK_PER 4      /* units per thread */", "#define RANK_PER 1")]
 VARS["RK2"] = [("#define RANK_PER 4      /* units per thread */", "#define RANK_PER 2")]
@@ -1205,13 +1209,11 @@ extern "C" __attribute__((visibility("default"))) int mp3d_dbg_hstat(unsigned lo
 # lane's big_values group stores, dead zero groups included, count1 stores,
 # UnitMeta), one atomic per unit, into g_hstat[3]
 VARS["HSTAT2"] = VARS["HSTAT"] + [
-    ("""                    uint4 pend = make_uint4(0u, 0u, 0u, 0u);
-                    bool held = false;""", """                    uint4 pend = make_uint4(0u, 0u, 0u, 0u);
-                    bool held = false;
+    ("""                    uint4 pend[HUFF_BURST - 1];""", """                    uint4 pend[HUFF_BURST - 1];
                     unsigned long long st_bytes = 56ull; /* UnitMeta: sf 40 B + 16 B */"""),
-    ("""                        if (held) { /* (k is uniform: no divergence) */""",
+    ("""                        const int slot = (k >> 3) % HUFF_BURST; /* (k is uniform: no divergence) */""",
      """                        st_bytes += 16ull;
-                        if (held) { /* (k is uniform: no divergence) */"""),
+                        const int slot = (k >> 3) % HUFF_BURST; /* (k is uniform: no divergence) */"""),
     ("""                        if (!two) {
                             c1_store(k, se0);""", """                        if (!two) {
                             st_bytes += 8ull;
@@ -1232,9 +1234,7 @@ VARS["HSTAT2"] = VARS["HSTAT"] + [
 # the pair-to-pair dependency chain (the funnel shift still uses the current
 # position): the most a register-resident bit buffer could take off k_huffman
 VARS["WPRE"] = [
-    ("""                    uint4 pend = make_uint4(0u, 0u, 0u, 0u);
-                    bool held = false;""", """                    uint4 pend = make_uint4(0u, 0u, 0u, 0u);
-                    bool held = false;
+    ("""                    uint4 pend[HUFF_BURST - 1];""", """                    uint4 pend[HUFF_BURST - 1];
                     uint32_t pw0, pw1, pw2;
                     {
                         const uint32_t w = (pos + 31u) >> 5;

@@ -74,18 +74,32 @@ __global__ void __launch_bounds__(HUFF_BLOCK) k_huffman(const uint8_t *__restric
                                                         const DevTables *__restrict__ tab, int16_t *__restrict__ is_buf,
                                                         UnitMeta *__restrict__ meta, int n_units, int F,
                                                         uint32_t *__restrict__ work, const uint32_t *__restrict__ perm) {
-    __shared__ __attribute__((aligned(16))) uint16_t s_lut[MP3D_LUT_MAX];
-    /* per-wave staging areas after a 4-word guard: win64g / win32g read the
-     * word below a window that starts on a word boundary */
-    __shared__ __attribute__((aligned(16))) uint32_t s_bits[4 + HUFF_WAVES * (HUFF_CAPW + 4)];
-    __shared__ uint32_t s_tsel[32]; /* table_select -> LUT base | (32 - bits1) << 16 | linbits << 24 */
-    __shared__ uint16_t s_lbnd[9][24]; /* long sfb start line per sample-rate index (23 bounds) */
-    __shared__ uint8_t s_slen[32];     /* MPEG-1 slen1 | slen2 per scalefac_compress          */
-    /* count1 values with their signs, by (value bits v, the 4 bits after the
-     * code): signed bytes [q2, q0, q3, q1], so each 2 x int16 output word is
-     * one v_perm_b32 (sign-extension selectors read odd bytes only) */
-    __shared__ uint32_t s_c1s[256];
+    /* one object, so the layout is the declaration's: the tables lie below
+     * 64 KB, where their base is the LDS instructions' 16-bit offset field
+     * (above the staging areas, each base sat in a VGPR for the whole launch) */
+    struct HuffLds {
+        uint16_t lut[MP3D_LUT_MAX];
+        uint32_t tsel[32]; /* table_select -> LUT base | (32 - bits1) << 16 | linbits << 24 */
+        /* count1 values with their signs, by (value bits v, the 4 bits after the
+         * code): signed bytes [q2, q0, q3, q1], so each 2 x int16 output word is
+         * one v_perm_b32 (sign-extension selectors read odd bytes only) */
+        uint32_t c1s[256];
+        uint16_t lbnd[9][24]; /* long sfb start line per sample-rate index (23 bounds) */
+        uint8_t slen[32];     /* MPEG-1 slen1 | slen2 per scalefac_compress          */
+        /* per-wave staging areas after a 4-word guard: win64g / win32g read the
+         * word below a window that starts on a word boundary */
+        __attribute__((aligned(16))) uint32_t bits[4 + HUFF_WAVES * (HUFF_CAPW + 4)];
+    };
+    static_assert(sizeof(HuffLds) <= 160 * 1024 && sizeof(HuffLds) - sizeof(HuffLds::bits) <= HUFF_TAB_BYTES,
+                  "k_huffman: one workgroup fills a CU's LDS");
+    __shared__ __attribute__((aligned(16))) HuffLds s_lds;
     MP3D_LDS_ENTRY();
+    uint16_t(&s_lut)[MP3D_LUT_MAX] = s_lds.lut;
+    uint32_t(&s_tsel)[32] = s_lds.tsel;
+    uint32_t(&s_c1s)[256] = s_lds.c1s;
+    uint16_t(&s_lbnd)[9][24] = s_lds.lbnd;
+    uint8_t(&s_slen)[32] = s_lds.slen;
+    uint32_t *const s_bits = s_lds.bits;
     huff_tables_lane(tab, s_lut, s_tsel, s_lbnd, s_slen);
     static_assert(HUFF_BLOCK >= 256, "s_c1s: one entry per thread");
     if (threadIdx.x < 256) {
@@ -101,14 +115,20 @@ __global__ void __launch_bounds__(HUFF_BLOCK) k_huffman(const uint8_t *__restric
                              (uint32_t)(uint8_t)q[1] << 24;
     }
     __syncthreads();
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int wv = threadIdx.x >> 6;
     uint32_t *bits = s_bits + 4 + wv * (HUFF_CAPW + 4);
-    const uint32_t qbase = tab->lut_hdr.base[MP3D_LUT_TABLES - 1];
-    const int qb1 = tab->lut_hdr.bits1[MP3D_LUT_TABLES - 1];
+    /* (uniform, and said so: as loaded values they sat in VGPRs for the whole launch) */
+    const uint32_t qbase = (uint32_t)__builtin_amdgcn_readfirstlane((int)tab->lut_hdr.base[MP3D_LUT_TABLES - 1]);
+    const int qb1 = __builtin_amdgcn_readfirstlane((int)tab->lut_hdr.bits1[MP3D_LUT_TABLES - 1]);
     /* count1 table B: after the zero table (huff_tables_lane) */
     const uint32_t c1b_base = ((qbase + (1u << qb1) + 1u) & ~1u) + MP3D_C1B_OFF;
+    /* floor((2^32 - 1) / F), scalar: a frame's stream fr / F is then the high
+     * word of fr * f_inv, short by one at most (fr < 2^32); the compiler's own
+     * division kept its reciprocal in a VGPR for the whole launch */
+    const uint32_t f_inv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(0xFFFFFFFFu / (uint32_t)F));
     for (;;) {
         uint32_t t = 0u;
+        const int lane = lane_now(); /* (re-derived each round, not held through it) */
         if (lane == 0) t = atomicAdd(work, 1u);
         const int ubase = 64 * (int)__builtin_amdgcn_readfirstlane(t);
         if (ubase >= n_units) break;
@@ -118,21 +138,35 @@ __global__ void __launch_bounds__(HUFF_BLOCK) k_huffman(const uint8_t *__restric
             bool valid = u < n_units;
             /* the stream's md base, loaded together with the frame record (not
              * after it: one memory latency less per round) */
-            const uint64_t mdo = md_off[(valid ? fr : 0) / F];
-            FrameRec r;
+            const uint32_t frv = valid ? (uint32_t)fr : 0u;
+            uint32_t strm = __umulhi(frv, f_inv); /* fr / F, or one short of it */
+            strm += frv - strm * (uint32_t)F >= (uint32_t)F;
+            const uint64_t mdo = md_off[strm];
+            /* of the frame record the round keeps first_gr, nch, md_bit and
+             * rk = lsf | sr_idx << 8 (one register, not the record's words) */
             uint64_t sq[4] = {0, 0, 0, 0};
+            int first_gr = 0, nch = 1;
+            uint32_t rk = 0u, r_md_bit = 0u;
             if (valid) {
-                r = rec[fr];
+                const FrameRec r = rec[fr];
                 valid = r.frame_bytes && !(r.first_gr & (REC_TAG | REC_DROP)) && ch < r.nch && (gr == 0 || !r.lsf);
                 const ulonglong2 a = *(const ulonglong2 *)&sideu[u & ~3];
                 const ulonglong2 b = *(const ulonglong2 *)&sideu[(u & ~3) + 2];
                 sq[0] = a.x; sq[1] = a.y; sq[2] = b.x; sq[3] = b.y;
+                first_gr = valid ? (r.first_gr & 3) : 0;
+                nch = valid ? r.nch : 1;
+                rk = (uint32_t)r.lsf | (uint32_t)r.sr_idx << 8;
+                r_md_bit = r.md_bit;
             }
-            const int first_gr = valid ? (r.first_gr & 3) : 0;
-            const int nch = valid ? r.nch : 1;
+            __asm__("" : "+v"(rk));
+#define R_LSF (rk & 0xFFu)
+#define R_SR (rk >> 8)
             const bool dec = valid && gr >= first_gr;
             const int q = u & 3;
             const uint64_t side = sq[q];
+            /* granule 0's side word of this channel (scfsi reuse), picked here:
+             * the four words need not live through the decode */
+            const uint64_t side_g0 = sq[ch];
             const uint32_t p23 = dec ? (uint32_t)(side >> 52) : 0u;
             /* unit start = md_bit + part2_3 lengths of the frame's earlier
              * decoded units (gr >= first_gr, ch < nch) */
@@ -140,12 +174,12 @@ __global__ void __launch_bounds__(HUFF_BLOCK) k_huffman(const uint8_t *__restric
 #pragma unroll
             for (int qq = 0; qq < 3; qq++)
                 if (qq < q && (qq >> 1) >= first_gr && (qq & 1) < nch) before += (uint32_t)(sq[qq] >> 52);
-            const uint32_t start = dec ? r.md_bit + before : 0u;
+            const uint32_t start = dec ? r_md_bit + before : 0u;
             const int scfsi_raw = (int)(side >> 1) & 15;
             const bool long_blk = !(((side >> 30) & 1) && ((side >> 28) & 3) == 2);
             const int scfsi = (gr == 1 && long_blk) ? scfsi_raw : 0;
             const bool need_g0 = dec && scfsi && first_gr == 0;
-            const uint32_t g0_start = r.md_bit + (ch ? (uint32_t)(sq[0] >> 52) : 0u);
+            const uint32_t g0_start = r_md_bit + (ch ? (uint32_t)(sq[0] >> 52) : 0u);
             /* the lane's staged words: for scfsi reuse (need_g0) first a piece
              * of HUFF_G0W words at granule 0's scalefactors (their <= 126 bits
              * from any bit offset, plus the window margin), then the unit's own
@@ -191,7 +225,7 @@ __global__ void __launch_bounds__(HUFF_BLOCK) k_huffman(const uint8_t *__restric
                     const uint32_t seg = 32u * (off - base + lenA) - 32u * w0; /* md bit -> staged bit */
                     uint32_t pos = start + seg;
                     int lsf_pre = 0;
-                    if (r.lsf) {
+                    if (R_LSF) {
                         /* off the MPEG-1 path: a call keeps its registers out of
                          * the kernel's allocation; bits passed as an LDS pointer */
                         const uint32_t pp = read_sf_lsf((lds_cu32)bits, pos, side, (uint8_t *)&meta[u]);
@@ -204,7 +238,7 @@ __global__ void __launch_bounds__(HUFF_BLOCK) k_huffman(const uint8_t *__restric
                         if (need_g0) {
                             /* scfsi reuse: granule 0's scalefactors of this channel
                              * first, then granule 1's read over them in place */
-                            read_sf(bits, g0_start + seg - 32u * (lenA - dA), sq[ch], 0, sfw, s_slen); /* (its piece) */
+                            read_sf(bits, g0_start + seg - 32u * (lenA - dA), side_g0, 0, sfw, s_slen); /* (its piece) */
                         }
                         pos = read_sf(bits, pos, side, scfsi, sfw, s_slen);
                         uint8_t *mrec = (uint8_t *)&meta[u];
@@ -221,7 +255,7 @@ __global__ void __launch_bounds__(HUFF_BLOCK) k_huffman(const uint8_t *__restric
                         /* region0: 36 lines; FFmpeg LSF: 54 for long-type units
                          * (108 at 8 kHz), 72 for short units at 8 kHz */
                         const bool sh = ((side >> 28) & 3) == 2;
-                        r1 = r.sr_idx < 3 ? 36 : sh ? (r.sr_idx == 8 ? 72 : 36) : (r.sr_idx == 8 ? 108 : 54);
+                        r1 = R_SR < 3 ? 36 : sh ? (R_SR == 8 ? 72 : 36) : (R_SR == 8 ? 108 : 54);
                         r2 = 576;
                         ts0 = s_tsel[(side >> 22) & 31];
                         ts1 = s_tsel[(side >> 17) & 31];
@@ -231,8 +265,8 @@ __global__ void __launch_bounds__(HUFF_BLOCK) k_huffman(const uint8_t *__restric
                         const int b1 = rc0 + 1;
                         int b2 = rc0 + rc1 + 2;
                         if (b2 > 22) b2 = 22;
-                        r1 = s_lbnd[r.sr_idx][b1];
-                        r2 = s_lbnd[r.sr_idx][b2];
+                        r1 = s_lbnd[R_SR][b1];
+                        r2 = s_lbnd[R_SR][b2];
                         ts0 = s_tsel[(side >> 25) & 31];
                         ts1 = s_tsel[(side >> 20) & 31];
                         ts2 = s_tsel[(side >> 15) & 31];
@@ -249,13 +283,24 @@ __global__ void __launch_bounds__(HUFF_BLOCK) k_huffman(const uint8_t *__restric
                     int16_t *row = is_buf + (size_t)u * MP3D_IS_ROW;
                     int k = 0;
                     const uint32_t end_bit = start + seg + p23;
-                    /* stored two groups at a time: a lane writes 32 B (a whole
-                     * sector of its row's line) per store pair, not 16 B per
-                     * group -- a line evicted before the lane completes it then
-                     * holds only whole sectors (A/B ST32: -2.7 % k_huffman) */
-                    uint4 pend = make_uint4(0u, 0u, 0u, 0u);
-                    bool held = false;
-                    for (; __ballot(k < bv2); k += 8) {
+                    /* stored HUFF_BURST groups at a time, back to back: a lane
+                     * writes its row in aligned bursts of 16 HUFF_BURST bytes
+                     * (8 groups: one whole 128-B line; rows are 9 lines from a
+                     * line-aligned base), not 16 B per group -- a line is
+                     * open for the length of one burst, not for the ~32 pairs
+                     * of decode between its first and last group, so it
+                     * leaves L2 whole (A/B ST32, two groups: -2.7 %
+                     * k_huffman).  The burst's first groups wait in registers;
+                     * slot is uniform, so the slot tests are scalar branches
+                     * and a group moves into its slot by 4 moves (the empty asm
+                     * keeps the branches from becoming 4 selects per slot).
+                     * The loop is bottom-tested, its body written out here:
+                     * top-tested, or with the group decode in a lambda, the
+                     * compiler copied the whole buffer around the loop. */
+                    uint4 pend[HUFF_BURST - 1];
+#pragma unroll
+                    for (int i = 0; i < HUFF_BURST - 1; i++) pend[i] = make_uint4(0u, 0u, 0u, 0u);
+                    if (__ballot(k < bv2)) do {
                         uint32_t wv[4];
 #pragma unroll
                         for (int j = 0; j < 4; j++) {
@@ -298,15 +343,32 @@ __global__ void __launch_bounds__(HUFF_BLOCK) k_huffman(const uint8_t *__restric
                             wv[j] = live ? __builtin_amdgcn_perm((uint32_t)Y, (uint32_t)X, 0x05040100u) : 0u;
                         }
                         const uint4 cur = make_uint4(wv[0], wv[1], wv[2], wv[3]);
-                        if (held) { /* (k is uniform: no divergence) */
-                            *(uint4 *)(row + k - 8) = pend;
+                        const int slot = (k >> 3) % HUFF_BURST; /* (k is uniform: no divergence) */
+                        if (slot == HUFF_BURST - 1) {
+#pragma unroll
+                            for (int i = 0; i < HUFF_BURST - 1; i++)
+                                *(uint4 *)(row + k - 8 * (HUFF_BURST - 1 - i)) = pend[i];
                             *(uint4 *)(row + k) = cur;
                         } else {
-                            pend = cur;
+#pragma unroll
+                            for (int i = 0; i < HUFF_BURST - 1; i++)
+                                if (slot == i) {
+                                    __asm__ volatile("");
+                                    pend[i] = cur;
+                                }
                         }
-                        held = !held;
+                        k += 8;
+                    } while (__ballot(k < bv2));
+                    /* the partial last burst, before the count1 stores
+                     * overwrite its tail (a wave's stores to one address land
+                     * in issue order); for a lane already past its own
+                     * big_values these are zero groups, as in a full burst */
+                    {
+                        const int held = (k >> 3) % HUFF_BURST;
+#pragma unroll
+                        for (int i = 0; i < HUFF_BURST - 1; i++)
+                            if (i < held) *(uint4 *)(row + k - 8 * (held - i)) = pend[i];
                     }
-                    if (held) *(uint4 *)(row + k - 8) = pend; /* (before the count1 stores overwrite its tail) */
                     k = bv2;
                     /* count1 quadruples until the part2_3 end; a quadruple that
                      * overreads it is discarded (FFmpeg); lines
@@ -366,14 +428,14 @@ __global__ void __launch_bounds__(HUFF_BLOCK) k_huffman(const uint8_t *__restric
                     m.block_type = (uint8_t)(ws ? (side >> 28) & 3 : 0);
                     m.mixed = (uint8_t)(ws && ((side >> 28) & 3) == 2 ? (side >> 27) & 1 : 0);
                     m.scalefac_scale = (uint8_t)((side >> 6) & 1);
-                    m.preflag = (uint8_t)(r.lsf ? lsf_pre : (int)((side >> 7) & 1));
+                    m.preflag = (uint8_t)(R_LSF ? lsf_pre : (int)((side >> 7) & 1));
                     m.sbg[0] = (uint8_t)(ws ? (side >> 14) & 7 : 0);
                     m.sbg[1] = (uint8_t)(ws ? (side >> 11) & 7 : 0);
                     m.sbg[2] = (uint8_t)(ws ? (side >> 8) & 7 : 0);
                     m.nz_end = (uint16_t)nz_end;
                     m.part2_3_length = (uint16_t)p23;
                     m.used_bits = (uint16_t)(pos - start - seg);
-                    m.flags = (uint16_t)(r.lsf ? ((side >> 31) & 1) << 1 : 0); /* LSF intensity_scale */
+                    m.flags = (uint16_t)(R_LSF ? ((side >> 31) & 1) << 1 : 0); /* LSF intensity_scale */
                     /* everything after sf[40]: one 16-B store */
                     *(uint4 *)((uint8_t *)&meta[u] + 40) = *(const uint4 *)((const uint8_t *)&m + 40);
                 }
@@ -391,19 +453,22 @@ __global__ void __launch_bounds__(HUFF_BLOCK) k_huffman(const uint8_t *__restric
                 m.block_type = (uint8_t)(ws ? (side >> 28) & 3 : 0);
                 m.mixed = (uint8_t)(ws && ((side >> 28) & 3) == 2 ? (side >> 27) & 1 : 0);
                 m.scalefac_scale = (uint8_t)((side >> 6) & 1);
-                m.preflag = (uint8_t)(r.lsf ? 0 : (int)((side >> 7) & 1));
+                m.preflag = (uint8_t)(R_LSF ? 0 : (int)((side >> 7) & 1));
                 m.sbg[0] = (uint8_t)(ws ? (side >> 14) & 7 : 0);
                 m.sbg[1] = (uint8_t)(ws ? (side >> 11) & 7 : 0);
                 m.sbg[2] = (uint8_t)(ws ? (side >> 8) & 7 : 0);
                 m.nz_end = 0;
                 m.part2_3_length = 0;
                 m.used_bits = 0;
-                m.flags = (uint16_t)(1 | (r.lsf ? ((side >> 31) & 1) << 1 : 0));
+                m.flags = (uint16_t)(1 | (R_LSF ? ((side >> 31) & 1) << 1 : 0));
                 meta[u] = m;
             }
         }
     }
 }
+
+#undef R_LSF
+#undef R_SR
 
 /* k_huffman_wave: one wave per unit (huffman_wave_unit, mp3d_huffman_dev.h) */
 __global__ void __launch_bounds__(64 * HW_UNITS) k_huffman_wave(const uint8_t *__restrict__ md,

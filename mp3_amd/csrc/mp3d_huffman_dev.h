@@ -23,16 +23,37 @@ namespace mp3d {
 /* runs max(big_values) iterations per wave whatever the region tables.     */
 /* Side info arrives pre-extracted by k_demux (one u64 per unit).           */
 /* ------------------------------------------------------------------------ */
-/* One 16-wave workgroup per CU (4 waves per SIMD at <= 128 VGPRs), sharing
+/* One 12-wave workgroup per CU (3 waves per SIMD at <= 168 VGPRs), sharing
  * one copy of the LUT; the waves take 64-unit rounds of the launch's
  * big_values order from a work counter (persistent).  4-wave workgroups held
  * 3 LUT copies per CU and fit only 3 waves per SIMD beside the staging
- * areas. */
-#define HUFF_WAVES 16
+ * areas.  16 waves (4 per SIMD at <= 128 VGPRs) have neither the registers
+ * for whole-line store bursts nor the LDS to stage most rounds in one batch
+ * (2 304 words a wave against 3 076): 12 waves with both run k_huffman 11 %
+ * faster on C3 (profiles/r07_huff_bursts.txt). */
+#ifndef HUFF_WAVES
+#define HUFF_WAVES 12 /* 12, or 16 (A/B builds: -DHUFF_WAVES=16 -DHUFF_BURST=2) */
+#endif
+/* big_values groups (16 B) a lane stores back to back: 8 = one whole 128-B
+ * line of its is[] row; HUFF_BURST - 1 groups (4 VGPRs each) wait in
+ * registers (2 or 4: 32- or 64-B bursts; 4 does not fit 128 VGPRs) */
+#ifndef HUFF_BURST
+#define HUFF_BURST 8
+#endif
 #define MP3D_C1B_OFF 2 /* count1 table B after the zero table (huff_tables_lane) */
 #define HUFF_BLOCK (64 * HUFF_WAVES)
-#define HUFF_CAPW 2304 /* LDS words per wave (9.2 KB) of main-data staging; 16 waves + the tables in 160 KB */
-#define HUFF_STAGEW HUFF_CAPW /* staging words */
+/* k_huffman's LDS tables (s_lut, s_tsel, s_lbnd, s_slen, s_c1s) + 32 B of
+ * alignment padding; the staging areas take what the CU's 160 KB leave */
+#define HUFF_TAB_BYTES (2 * MP3D_LUT_MAX + 4 * 32 + 2 * 9 * 24 + 32 + 4 * 256 + 32)
+/* LDS words per wave of main-data staging, a 16-B multiple, beside each
+ * area's 4-word guard (+ one more below the first): 2 304 (9.2 KB) at 16
+ * waves, 3 076 (12.3 KB) at 12 */
+#define HUFF_CAPW ((((160 * 1024 - HUFF_TAB_BYTES) / 4 - 4) / HUFF_WAVES - 4) & ~3)
+#define HUFF_STAGEW HUFF_CAPW /* staging words: the whole area */
+static_assert(HUFF_WAVES == 12 || HUFF_WAVES == 16, "k_huffman: 3 or 4 waves per SIMD");
+static_assert(HUFF_BURST == 2 || HUFF_BURST == 4 || HUFF_BURST == 8,
+              "k_huffman: aligned bursts of 32, 64 or 128 B (a line holds a whole number)");
+static_assert(HUFF_WAVES != 16 || HUFF_CAPW == 2304, "k_huffman: the 16-wave staging area");
 #define HUFF_G0W 8u /* words staged at granule 0's scalefactors for scfsi reuse (<= 31 + 126 bits + the window margin) */
 
 /* wave-wide scan / min by ds_bpermute with the lane id re-derived at each
