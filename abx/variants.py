@@ -856,7 +856,7 @@ VARS["PHT2"] = [
      "    float *const sBuf = Wd.buf;\n    unsigned long long ph_[8] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull}, tQ_ = 0ull, tI_ = 0ull, tM_ = 0ull, tW_ = 0ull, tE_ = 0ull, t1_ = 0ull, t2_ = 0ull;\n"),
     (_QS, "            tQ_ = clock64(); if (tE_) ph_[7] += tQ_ - tE_;\n" + _QS),
     ("                (void)m12a;\n", "                (void)m12a;\n                t1_ = clock64(); ph_[4] += t1_ - tQ_;\n"),
-    ("                xin();\n                } /* !fusedq */", "                t2_ = clock64(); ph_[5] += t2_ - t1_;\n                xin();\n                } /* !fusedq */"),
+    ("                xin(xin_off);\n                } /* !fusedq */", "                t2_ = clock64(); ph_[5] += t2_ - t1_;\n                xin(xin_off);\n                } /* !fusedq */"),
     (_IS, "            tI_ = clock64(); ph_[0] += tI_ - tQ_; ph_[6] += tI_ - t2_;\n" + _IS),
     (_MS, "            tM_ = clock64(); ph_[1] += tM_ - tI_;\n" + _MS),
     (_WS, "            tW_ = clock64(); ph_[2] += tW_ - tM_;\n" + _WS),
@@ -879,7 +879,7 @@ VARS["PHT3"] = [
      "                else requant(std::integral_constant<int, 5>{});\n                __asm__ volatile(\"s_waitcnt lgkmcnt(0)\" : \"+v\"(xp[0][0]), \"+v\"(xp[1][0]));\n                tb_ = clock64(); ph_[1] += tb_ - ta_;\n"),
     ("                if (ms_fold) {\n",
      "                tc_ = clock64(); ph_[2] += tc_ - tb_;\n                if (ms_fold) {\n"),
-    ("                xin();\n                } /* !fusedq */", "                ph_[3] += clock64() - tc_;\n                xin();\n                } /* !fusedq */"),
+    ("                xin(xin_off);\n                } /* !fusedq */", "                ph_[3] += clock64() - tc_;\n                xin(xin_off);\n                } /* !fusedq */"),
     ("    if (f1 == F && PF != 1) {",
      "    if ((blockIdx.x == 0 || blockIdx.x == 4000) && threadIdx.x == 0 && !SRC_XR && !LSF)\n"
      "        printf(\"PHT3 blk %d cis %llu requant %llu esc+stereo %llu scatter %llu\\n\", (int)blockIdx.x, ph_[0], ph_[1], ph_[2], ph_[3]);\n"

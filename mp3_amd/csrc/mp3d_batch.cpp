@@ -247,6 +247,13 @@ static bool demux_wide(int n) {
     return n >= MP3D_WIDE_STREAMS;
 }
 
+/* MP3D_SYNTH_LONGPATH=0 sends every granule through k_synth's general phase
+ * Q and alias step (tests compare the two paths bit for bit); default on */
+static bool synth_longpath() {
+    const char *e = getenv("MP3D_SYNTH_LONGPATH");
+    return !(e && !strcmp(e, "0"));
+}
+
 /* batches of at most this many units (frame granule channels) decode one
  * unit per wave (k_huffman_wave); MP3D_HUFF=wave | lane forces the kernel */
 #define MP3D_WAVE_HUFF_UNITS 1024
@@ -416,7 +423,7 @@ int mp3d::batch_decode(mp3d_batch *b, const uint8_t *frames, const uint64_t *off
     if (r) return r;
     if (b->poison) launch_lds_poison(dc.n_cu, s);
     launch_synth(b->rec, b->is_buf, b->meta, dc.tables, b->st, dpcm, f32, n, F, kinds, seg_len, tp.out, tp.in,
-                 b->fam_ok ? b->d_work + 1 : nullptr, b->call_seq, dc.n_cu, s);
+                 b->fam_ok ? b->d_work + 1 : nullptr, b->call_seq, dc.n_cu, synth_longpath(), s);
     if (b->timing) HIPCHK(hipEventRecord(b->ev[3], s));
     HIPCHK(hipGetLastError());
     tail_commit(b, n, F, seg_len, tp);

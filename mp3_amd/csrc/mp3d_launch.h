@@ -47,10 +47,12 @@ void launch_frame(const uint8_t *in_host, uint32_t in_have, const uint64_t *in_o
                   uint8_t *md, const uint64_t *md_off, StreamState *st, FrameRec *rec, uint64_t *sideu, void *infos,
                   int opts, const DevTables *tab, int16_t *is_buf, UnitMeta *meta, void *pcm, bool f32, bool lsf,
                   uint32_t *done, uint32_t seq, hipStream_t strm);
-/* k_synth: requantize to PCM, the family variants in kinds, in segments of seg_len frames */
+/* k_synth: requantize to PCM, the family variants in kinds, in segments of seg_len frames; longpath: all-long
+ * M/S granules take phase Q's and the alias step's straight-line path (off: every granule the general one) */
 void launch_synth(const FrameRec *rec, const int16_t *is_buf, const UnitMeta *meta, const DevTables *tab,
                   StreamState *st, void *pcm, bool f32, int n_streams, int F, int kinds, int seg_len, float *st_tail,
-                  const float *st_tail_in, const uint32_t *fam, uint32_t seq, int n_cu, hipStream_t strm);
+                  const float *st_tail_in, const uint32_t *fam, uint32_t seq, int n_cu, bool longpath,
+                  hipStream_t strm);
 /* k_synth from caller-supplied spectra (mp3d_batch_synth_only) */
 void launch_synth_xr(const float *xr, const uint8_t *bt, const uint8_t *mixed, const DevTables *tab, StreamState *st,
                      int16_t *pcm, int n_streams, int F, int nch, int sr, int seg_len, float *st_tail,

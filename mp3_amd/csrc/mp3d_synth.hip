@@ -322,7 +322,7 @@ __device__ __forceinline__ void synth_tables(SynShared<LSF> &T, const DevTables 
  * 2 = granule 1 only, taking them from xch, state out.  The two waves meet
  * at two workgroup barriers (every other wave of the workgroup runs two
  * as well). */
-template <bool SRC_XR, bool F32, bool LSF, int PF = 0>
+template <bool SRC_XR, bool F32, bool LSF, int PF = 0, bool LONGQ = false>
 __device__ __forceinline__ void synth_stream(const FrameRec *__restrict__ rec, const int16_t *__restrict__ is_buf,
                                              const UnitMeta *__restrict__ meta, const float *__restrict__ xr_in,
                                              const uint8_t *__restrict__ xr_bt, const uint8_t *__restrict__ xr_mixed,
@@ -704,6 +704,16 @@ __device__ __forceinline__ void synth_stream(const FrameRec *__restrict__ rec, c
              * synth-only entry measured within noise, so it stays at 0) */
             if (!SRC_XR) __builtin_amdgcn_s_setprio(1);
             bool fusedq = false; /* phase Q's fused requantiser ran */
+            /* all-long granule (uniform): long blocks in every coded channel,
+             * no intensity stereo, not the fused requantiser's -- which leaves
+             * the M/S-only stereo granules.  Phase Q and the alias step take
+             * their straight-line forms (kernel variant LONGQ; off: today's).
+             * Evaluated from the frame's mode words and the block types where
+             * phase Q and phase I branch on it: held from one to the other it
+             * took an SGPR the loop does not have */
+            auto all_long = [&]() {
+                return PAR && LONGQ && nch == 2 && mode == 1 && mext == 2 && bt0 != 2 && bt1 != 2;
+            };
             /* phase I's input: lane (ch, sb)'s 18 lines and the alias
              * neighbours up[k] = x_{sb-1}[17 - k], dn[k] = x_{sb+1}[k] */
             float xf[18], up[8], dn[8];
@@ -711,10 +721,10 @@ __device__ __forceinline__ void synth_stream(const FrameRec *__restrict__ rec, c
              * land), at the end of each scatter path of phase Q (as one
              * read after the paths merge, the fused path's xf was held
              * across the scatter paths' registers and spilled) */
-            auto xin = [&]() {
+            auto xin = [&](uint32_t xoff) {
                 wave_sync();
                 typedef __attribute__((address_space(3))) const f32x2 lds_cf2;
-                lds_cf2 *const P = (lds_cf2 *)(uintptr_t)((uint32_t)(uintptr_t)(lds_cf32 *)(const float *)sBuf + xin_off);
+                lds_cf2 *const P = (lds_cf2 *)(uintptr_t)((uint32_t)(uintptr_t)(lds_cf32 *)(const float *)sBuf + xoff);
 #pragma unroll
                 for (int i = 0; i < 9; i++) {
                     const f32x2 v = P[4 + i];
@@ -770,7 +780,7 @@ __device__ __forceinline__ void synth_stream(const FrameRec *__restrict__ rec, c
                         }
                     }
                 }
-                xin();
+                xin(xin_off);
             } else {
                 /* nz_end per channel (UnitMeta word 12, uniform): the 128-line
                  * chunks i at or past max(nz_end) are all zero, so their
@@ -819,6 +829,7 @@ __device__ __forceinline__ void synth_stream(const FrameRec *__restrict__ rec, c
                  * VALU per granule cost more than the LDS round trip saved
                  * (A/B FQ: C3 +2 % k_synth) */
                 fusedq = PAR && var[0] == 0 && var[1] == 0 && !is_on && !ms_fold;
+                const bool longq = all_long(); /* = long / long, !is_on, !fusedq: M/S only */
                 const float rsq2 = 0.70710678118654752f;
                 /* per-band scale 2^(q/4), lane = band idx (long b | 22 + 3 b + w);
                  * the lane's scalefactor byte comes from the prefetched meta
@@ -925,6 +936,89 @@ __device__ __forceinline__ void synth_stream(const FrameRec *__restrict__ rec, c
                         up[k] = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(xf[17 - k]), 0x138, 0xF, 0xF, false));
                         dn[k] = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(xf[k]), 0x130, 0xF, 0xF, false));
                     }
+                } else if (longq) {
+                    /* all-long M/S granule: one straight-line copy per class
+                     * of live 128-line chunks (NI = 2, 3, 4, 5 by the largest
+                     * nz_end).  Line-pair row lpair[0], every store the in-
+                     * place 8-B one, (L + R, L - R) of the live chunks only
+                     * (1 / sqrt2 is in the band scales).  The dead lines must
+                     * still read as zero in xin (the buffer holds the previous
+                     * granule's X): chunk NI of both channels is stored as
+                     * zeros, which covers every window that starts below line
+                     * 128 NI (it ends within 26 lines of it), and the lanes
+                     * whose whole window [18 sb - 8, 18 sb + 26) lies at or
+                     * past 128 NI read channel 0's zero chunk instead of their
+                     * own lines: the same +0 the general path stores there. */
+                    auto qlong = [&](auto nic) {
+                        constexpr int NI = decltype(nic)::value;
+                        uint32_t w[2][NI];
+#pragma unroll
+                        for (int c = 0; c < 2; c++)
+#pragma unroll
+                            for (int i = 0; i < NI; i++) w[c][i] = isq[320 * c + 64 * i + lane];
+                        f32x2 x[2][NI];
+                        uint32_t big = 0u;
+#pragma unroll
+                        for (int i = 0; i < NI; i++) {
+                            /* chunk 4 is half a chunk: lanes < 32 */
+                            const uint32_t tv2 = (i < 4 || lane < 32) ? lpair[0][lane + 64 * i] : 0u;
+#pragma unroll
+                            for (int c = 0; c < 2; c++) {
+                                uint32_t t;
+                                __asm__("v_pk_mad_u16 %0, %1, 4, %2 op_sel_hi:[1,0,0]" : "=v"(t) : "v"(w[c][i]), "s"(k1024));
+                                big |= t;
+                                const float sc = *(lds_cf32 *)(uintptr_t)(sc_base[c] | (tv2 & 0xFCu));
+                                x[c][i] = (f32x2){*(const float *)(p43b + (t & 0x7FCu)) * sc,
+                                                  *(const float *)(p43b + ((t >> 16) & 0x7FCu)) * sc};
+                            }
+                        }
+                        if (__ballot((big & 0xF800F800u) != 0u)) {
+                            /* rare: escapes (|is| >= 256), patched as on the general path */
+#pragma unroll
+                            for (int i = 0; i < NI; i++) {
+#pragma unroll
+                                for (int c = 0; c < 2; c++) {
+#pragma unroll
+                                    for (int e = 0; e < 2; e++) {
+                                        const int v = (int)(int16_t)(e ? (w[c][i] >> 16) : (w[c][i] & 0xFFFFu));
+                                        const int a = v < 0 ? -v : v;
+                                        if ((uint32_t)(v + 256) >= 512u) {
+                                            const uint32_t tv2 = lpair[0][lane + 64 * i];
+                                            const float mag = pow43_big(a) * Wd.scale[c][(tv2 >> 2) & 63u];
+                                            x[c][i][e] = v < 0 ? -mag : mag;
+                                        }
+                                    }
+                                }
+                            }
+                        }
+#pragma unroll
+                        for (int i = 0; i < NI; i++)
+                            if (i < 4 || lane < 32) {
+                                *(f32x2 *)&sBuf[2 * lane + 128 * i] = x[0][i] + x[1][i];
+                                *(f32x2 *)&sBuf[576 + 2 * lane + 128 * i] = x[0][i] - x[1][i];
+                            }
+                        if constexpr (NI < 5) {
+                            /* (the zero pair made here: as a constant the
+                             * compiler held it in SGPRs across the loop, spilled) */
+                            f32x2 z0;
+                            __asm__ volatile("v_mov_b64 %0, 0" : "=v"(z0));
+                            if (NI < 4 || lane < 32) {
+                                *(f32x2 *)&sBuf[2 * lane + 128 * NI] = z0;
+                                *(f32x2 *)&sBuf[576 + 2 * lane + 128 * NI] = z0;
+                            }
+                            /* first subband whose window starts at or past line 128 NI */
+                            constexpr int SBD = (128 * NI + 8 + 17) / 18;
+                            static_assert(18 * SBD - 8 >= 128 * NI && 18 * (SBD - 1) + 26 <= 128 * NI + (NI < 4 ? 128 : 64),
+                                          "k_synth: the zero chunk covers the windows that reach it");
+                            xin((lane & 31) >= SBD ? (uint32_t)(128 * NI * 4) : xin_off);
+                        } else {
+                            xin(xin_off);
+                        }
+                    };
+                    if (nzmax <= 256) qlong(std::integral_constant<int, 2>{});
+                    else if (nzmax <= 384) qlong(std::integral_constant<int, 3>{});
+                    else if (nzmax <= 512) qlong(std::integral_constant<int, 4>{});
+                    else qlong(std::integral_constant<int, 5>{});
                 } else {
                 /* (read here, not before the band scales: read early, the
                  * words were held through the fused path and spilled) */
@@ -1075,7 +1169,7 @@ __device__ __forceinline__ void synth_stream(const FrameRec *__restrict__ rec, c
                                 if (c < nch) scatter(i, c, xp[c][i]);
                         }
                 }
-                xin();
+                xin(xin_off);
                 } /* !fusedq */
                 /* the next granule's loads fly during phases I, M, W (issued
                  * after phase Q read this granule's words), from ONE call
@@ -1114,6 +1208,88 @@ __device__ __forceinline__ void synth_stream(const FrameRec *__restrict__ rec, c
                  * each (they arrive as consecutive pairs from LDS; r03 AL1:
                  * with op_sel swizzles and LDS coefficient pairs -8 VALU but
                  * +3 VGPRs, 168 of 168) */
+                if (PAR && LONGQ) {
+                    /* upper and lower as two EXEC masks (uniform values: per
+                     * channel half all subbands but the first / last (long),
+                     * subband 1 / 0 (mixed), none (short)), the butterflies in
+                     * place under them, no selects: x[k] = fma(up[k], CA,
+                     * x[k] CS) reads only up[k] and x[k], x[17 - k] = fma(dn[k],
+                     * -CA, x[17 - k] CS) only dn[k] and x[17 - k] (-dn CA =
+                     * dn (-CA) exactly): per value the operations of the
+                     * general form below, and a lane outside the mask keeps
+                     * its line.  One asm block per half, which sets EXEC itself
+                     * (as conditional C++ the compiler built the divergent
+                     * branch noted above) and hands it back as -1: here every
+                     * lane of the wave is active (64-lane waves, wave-uniform
+                     * control flow down to this point).  Every granule of the
+                     * LONGQ kernel takes this form: on the all-long ones
+                     * alone, the merge with the select form cost 16 register
+                     * copies.  The coefficients are the table's bit patterns
+                     * as literals */
+                    const uint32_t mu0 = bt0 != 2 ? 0xFFFFFFFEu : (mx0 ? 2u : 0u), mu1 = bt1 != 2 ? 0xFFFFFFFEu : (mx1 ? 2u : 0u);
+                    const uint32_t ml0 = mu0 >> 1, ml1 = mu1 >> 1; /* sb <= 30 | sb == 0 | none */
+                    /* (readfirstlane: a no-op on values the compiler knows to
+                     * be uniform, and the masks in SGPRs where it does not) */
+                    auto m64 = [](uint32_t lo, uint32_t hi) {
+                        return (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)lo) |
+                               ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)hi) << 32);
+                    };
+                    const uint64_t mup = m64(mu0, mu1), mlo = m64(ml0, ml1);
+#define ALIAS_BITS(A, k, v) static_assert(__builtin_bit_cast(uint32_t, A[k]) == v, "alias literal " #A)
+                    ALIAS_BITS(MP3D_K_ALIAS_CS, 0, 0x3f5b84a8u); ALIAS_BITS(MP3D_K_ALIAS_CS, 1, 0x3f61b9d8u);
+                    ALIAS_BITS(MP3D_K_ALIAS_CS, 2, 0x3f731addu); ALIAS_BITS(MP3D_K_ALIAS_CS, 3, 0x3f7bba81u);
+                    ALIAS_BITS(MP3D_K_ALIAS_CS, 4, 0x3f7eda41u); ALIAS_BITS(MP3D_K_ALIAS_CS, 5, 0x3f7fc8fdu);
+                    ALIAS_BITS(MP3D_K_ALIAS_CS, 6, 0x3f7ff965u); ALIAS_BITS(MP3D_K_ALIAS_CS, 7, 0x3f7fff8du);
+                    ALIAS_BITS(MP3D_K_ALIAS_CA, 0, 0xbf03b5feu); ALIAS_BITS(MP3D_K_ALIAS_CA, 1, 0xbef186dau);
+                    ALIAS_BITS(MP3D_K_ALIAS_CA, 2, 0xbea07302u); ALIAS_BITS(MP3D_K_ALIAS_CA, 3, 0xbe3a4774u);
+                    ALIAS_BITS(MP3D_K_ALIAS_CA, 4, 0xbdc1b01du); ALIAS_BITS(MP3D_K_ALIAS_CA, 5, 0xbd27cb87u);
+                    ALIAS_BITS(MP3D_K_ALIAS_CA, 6, 0xbc68a11du); ALIAS_BITS(MP3D_K_ALIAS_CA, 7, 0xbb727b46u);
+#undef ALIAS_BITS
+                    __asm__ volatile("s_mov_b64 exec, %16\n\t"
+                                     "v_mul_f32 %0, 0x3f5b84a8, %0\n\t"
+                                     "v_mul_f32 %1, 0x3f61b9d8, %1\n\t"
+                                     "v_mul_f32 %2, 0x3f731add, %2\n\t"
+                                     "v_mul_f32 %3, 0x3f7bba81, %3\n\t"
+                                     "v_mul_f32 %4, 0x3f7eda41, %4\n\t"
+                                     "v_mul_f32 %5, 0x3f7fc8fd, %5\n\t"
+                                     "v_mul_f32 %6, 0x3f7ff965, %6\n\t"
+                                     "v_mul_f32 %7, 0x3f7fff8d, %7\n\t"
+                                     "v_fmac_f32 %0, 0xbf03b5fe, %8\n\t"
+                                     "v_fmac_f32 %1, 0xbef186da, %9\n\t"
+                                     "v_fmac_f32 %2, 0xbea07302, %10\n\t"
+                                     "v_fmac_f32 %3, 0xbe3a4774, %11\n\t"
+                                     "v_fmac_f32 %4, 0xbdc1b01d, %12\n\t"
+                                     "v_fmac_f32 %5, 0xbd27cb87, %13\n\t"
+                                     "v_fmac_f32 %6, 0xbc68a11d, %14\n\t"
+                                     "v_fmac_f32 %7, 0xbb727b46, %15\n\t"
+                                     "s_mov_b64 exec, -1"
+                                     : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]), "+v"(x[4]), "+v"(x[5]),
+                                       "+v"(x[6]), "+v"(x[7])
+                                     : "v"(up[0]), "v"(up[1]), "v"(up[2]), "v"(up[3]), "v"(up[4]), "v"(up[5]), "v"(up[6]),
+                                       "v"(up[7]), "s"(mup));
+                    __asm__ volatile("s_mov_b64 exec, %16\n\t"
+                                     "v_mul_f32 %0, 0x3f5b84a8, %0\n\t"
+                                     "v_mul_f32 %1, 0x3f61b9d8, %1\n\t"
+                                     "v_mul_f32 %2, 0x3f731add, %2\n\t"
+                                     "v_mul_f32 %3, 0x3f7bba81, %3\n\t"
+                                     "v_mul_f32 %4, 0x3f7eda41, %4\n\t"
+                                     "v_mul_f32 %5, 0x3f7fc8fd, %5\n\t"
+                                     "v_mul_f32 %6, 0x3f7ff965, %6\n\t"
+                                     "v_mul_f32 %7, 0x3f7fff8d, %7\n\t"
+                                     "v_fmac_f32 %0, 0x3f03b5fe, %8\n\t"
+                                     "v_fmac_f32 %1, 0x3ef186da, %9\n\t"
+                                     "v_fmac_f32 %2, 0x3ea07302, %10\n\t"
+                                     "v_fmac_f32 %3, 0x3e3a4774, %11\n\t"
+                                     "v_fmac_f32 %4, 0x3dc1b01d, %12\n\t"
+                                     "v_fmac_f32 %5, 0x3d27cb87, %13\n\t"
+                                     "v_fmac_f32 %6, 0x3c68a11d, %14\n\t"
+                                     "v_fmac_f32 %7, 0x3b727b46, %15\n\t"
+                                     "s_mov_b64 exec, -1"
+                                     : "+v"(x[17]), "+v"(x[16]), "+v"(x[15]), "+v"(x[14]), "+v"(x[13]),
+                                       "+v"(x[12]), "+v"(x[11]), "+v"(x[10])
+                                     : "v"(dn[0]), "v"(dn[1]), "v"(dn[2]), "v"(dn[3]), "v"(dn[4]), "v"(dn[5]), "v"(dn[6]),
+                                       "v"(dn[7]), "s"(mlo));
+                } else {
 #pragma unroll
                 for (int k = 0; k < 8; k++) {
                     const float lo = x[17 - k], hi = x[k];
@@ -1121,6 +1297,7 @@ __device__ __forceinline__ void synth_stream(const FrameRec *__restrict__ rec, c
                     const float nl = fmaf(-dn[k], MP3D_K_ALIAS_CA[k], lo * MP3D_K_ALIAS_CS[k]);
                     x[k] = upper ? nh : hi;
                     x[17 - k] = lower ? nl : lo;
+                }
                 }
                 const bool long_imdct = bt != 2 || (mixed && sb < 2);
                 if (long_imdct) {
@@ -1516,7 +1693,7 @@ template <bool SRC_XR, bool LSF> struct SynCfg {
     static constexpr int WAVES = DMA ? 8 : 4;
 };
 
-template <bool SRC_XR, bool F32, bool LSF>
+template <bool SRC_XR, bool F32, bool LSF, bool LONGQ = false>
 /* MPEG-1 decode and synth only: 4 waves / SIMD (<= 128 VGPRs), the next
  * granule's is[] words or channel-0 spectra prefetched by LDS-DMA into the
  * wave's isq area; LSF: 3 waves / SIMD (168 VGPRs).  (Round 2: without any
@@ -1582,9 +1759,9 @@ k_synth(const FrameRec *__restrict__ rec, const int16_t *__restrict__ is_buf, co
         if (vs >= n_streams * nseg) return false; /* after the only workgroup barrier */
         const int s = vs / nseg, seg = vs - s * nseg;
         if (!SRC_XR && (st[s].kind == 2) != LSF) return true; /* the other variant's stream */
-        synth_stream<SRC_XR, F32, LSF>(rec, is_buf, meta, xr_in, xr_bt, xr_mixed, tab, st, pcm, F, xr_nch, xr_sr,
-                                       seg_len, st_tail, st_tail_in, T, Wv[wid], s, seg, nseg, nullptr,
-                                       SynCfg<SRC_XR, LSF>::DMA ? s_isq[SynCfg<SRC_XR, LSF>::DMA ? wid : 0] : nullptr);
+        synth_stream<SRC_XR, F32, LSF, 0, LONGQ>(
+            rec, is_buf, meta, xr_in, xr_bt, xr_mixed, tab, st, pcm, F, xr_nch, xr_sr, seg_len, st_tail, st_tail_in, T,
+            Wv[wid], s, seg, nseg, nullptr, SynCfg<SRC_XR, LSF>::DMA ? s_isq[SynCfg<SRC_XR, LSF>::DMA ? wid : 0] : nullptr);
         return true;
     };
     if constexpr (LSF && !SRC_XR) {
@@ -1775,7 +1952,8 @@ void launch_frame(const uint8_t *in_host, uint32_t in_have, const uint64_t *in_o
  * (st_tail_in, when given, holds the streams' state in place of st) */
 void launch_synth(const FrameRec *rec, const int16_t *is_buf, const UnitMeta *meta, const DevTables *tab,
                   StreamState *st, void *pcm, bool f32, int n_streams, int F, int kinds, int seg_len, float *st_tail,
-                  const float *st_tail_in, const uint32_t *fam, uint32_t seq, int n_cu, hipStream_t strm) {
+                  const float *st_tail_in, const uint32_t *fam, uint32_t seq, int n_cu, bool longpath,
+                  hipStream_t strm) {
     const int waves = n_streams * ((F + seg_len - 1) / seg_len);
     /* the family variants in `kinds` (bit 0 MPEG-1, bit 1 LSF; a batch
      * launches both); a workgroup without a stream of its variant exits
@@ -1785,21 +1963,26 @@ void launch_synth(const FrameRec *rec, const int16_t *is_buf, const UnitMeta *me
      * once on an all-MPEG-1 batch (its 16 384 workgroups' dispatch and loads
      * cost 39 us per C3 step) */
     const int lsf_grid = 3 * (n_cu > 0 ? n_cu : 256);
-#define MP3D_SYNTH_LAUNCH(F32_, LSF_)                                                                              \
+    /* MPEG-1 only: the kernel with the all-long path (longpath), or the one
+     * whose every granule takes the general phase Q and alias step -- two
+     * instantiations, so the switch costs the granule loop no register */
+#define MP3D_SYNTH_LAUNCH(F32_, LSF_, LONGQ_)                                                                      \
     do {                                                                                                           \
         constexpr int NW = SynCfg<false, LSF_>::WAVES;                                                             \
         int nb = (waves + NW - 1) / NW;                                                                            \
         if (LSF_ && fam && nb > lsf_grid) nb = lsf_grid;                                                           \
-        hipLaunchKernelGGL((k_synth<false, F32_, LSF_>), dim3(nb), dim3(64 * NW), 0, strm, rec, is_buf, meta,       \
-                           (const float *)nullptr, (const uint8_t *)nullptr, (const uint8_t *)nullptr, tab, st, pcm,  \
-                           n_streams, F, 2, 0, seg_len, st_tail, st_tail_in, LSF_ ? fam : nullptr, seq);           \
+        hipLaunchKernelGGL((k_synth<false, F32_, LSF_, LONGQ_>), dim3(nb), dim3(64 * NW), 0, strm, rec, is_buf,     \
+                           meta, (const float *)nullptr, (const uint8_t *)nullptr, (const uint8_t *)nullptr, tab,   \
+                           st, pcm, n_streams, F, 2, 0, seg_len, st_tail, st_tail_in, LSF_ ? fam : nullptr, seq);   \
     } while (0)
     if (f32) {
-        if (kinds & 1) MP3D_SYNTH_LAUNCH(true, false);
-        if (kinds & 2) MP3D_SYNTH_LAUNCH(true, true);
+        if ((kinds & 1) && longpath) MP3D_SYNTH_LAUNCH(true, false, true);
+        if ((kinds & 1) && !longpath) MP3D_SYNTH_LAUNCH(true, false, false);
+        if (kinds & 2) MP3D_SYNTH_LAUNCH(true, true, false);
     } else {
-        if (kinds & 1) MP3D_SYNTH_LAUNCH(false, false);
-        if (kinds & 2) MP3D_SYNTH_LAUNCH(false, true);
+        if ((kinds & 1) && longpath) MP3D_SYNTH_LAUNCH(false, false, true);
+        if ((kinds & 1) && !longpath) MP3D_SYNTH_LAUNCH(false, false, false);
+        if (kinds & 2) MP3D_SYNTH_LAUNCH(false, true, false);
     }
 #undef MP3D_SYNTH_LAUNCH
 }

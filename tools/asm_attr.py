@@ -83,7 +83,7 @@ def classify(op):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--src", default="mp3d_synth.hip")
-    ap.add_argument("--kernel", default="_ZN4mp3d7k_synthILb0ELb0ELb0EE")
+    ap.add_argument("--kernel", default="_ZN4mp3d7k_synthILb0ELb0ELb0ELb1EE")
     ap.add_argument("--asm", default=None, help="existing .s (skips the compile)")
     ap.add_argument("--flags", default="-fno-slp-vectorize")
     args = ap.parse_args()

@@ -17,7 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--src", default="mp3d_synth.hip")
-    ap.add_argument("--kernel", default="_ZN4mp3d7k_synthILb0ELb0ELb0EE")
+    ap.add_argument("--kernel", default="_ZN4mp3d7k_synthILb0ELb0ELb0ELb1EE")
     ap.add_argument("--flags", default="-fno-slp-vectorize")
     ap.add_argument("--min-valu", type=int, default=0)
     args = ap.parse_args()

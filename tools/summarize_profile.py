@@ -66,9 +66,10 @@ def main():
             cs["mfma_util"] = cs["SQ_VALU_MFMA_BUSY_CYCLES"] / (cs["GRBM_GUI_ACTIVE"] / 8.0 * 1024)
             cs["mfma_f32_flop_per_launch"] = cs.get("SQ_INSTS_VALU_MFMA_MOPS_F32", 0.0) * 512
     (dst / (a.tag + "_pmc.json")).write_text(json.dumps(out, indent=1, sort_keys=True))
-    # the MPEG-1 int16 decode variant (k_synth<SRC_XR=false, F32=false, LSF=false>), or the
-    # synth-only one for C2; entries per workload config, read by bench.py
-    want = ("k_synth<true,false,false>",) if a.config == "c2" else ("k_synth<false,false,false>", "k_synth<false>")
+    # the MPEG-1 int16 decode variant (k_synth<SRC_XR=false, F32=false, LSF=false, LONGQ=true>; older
+    # records: without LONGQ), or the synth-only one for C2; entries per workload config, read by bench.py
+    want = (("k_synth<true,false,false,false>", "k_synth<true,false,false>") if a.config == "c2" else
+            ("k_synth<false,false,false,true>", "k_synth<false,false,false>", "k_synth<false>"))
     key = next((k for k in out if k.replace(" ", "") in want), None)
     synth = out.get(key, {})
     if "hbm_bytes_per_launch" in synth:

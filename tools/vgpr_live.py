@@ -114,7 +114,7 @@ def analyse(insts, labels):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--src", default="mp3d_synth.hip")
-    ap.add_argument("--kernel", default="_ZN4mp3d7k_synthILb0ELb0ELb0EE")
+    ap.add_argument("--kernel", default="_ZN4mp3d7k_synthILb0ELb0ELb0ELb1EE")
     ap.add_argument("--flags", default="-fno-slp-vectorize")
     ap.add_argument("--top", type=int, default=40)
     ap.add_argument("--asm", default=None, help="use this .s instead of compiling")
