@@ -729,6 +729,127 @@ MP3D_API int mp3d_batch_apply_gain(mp3d_batch *b, const float *samples, long lon
  * mp3d_batch_set_timing */
 MP3D_API int mp3d_batch_true_peak_time(mp3d_batch *b, float *us);
 
+/* ---- tempo sink (pitch-preserving time stretch, WSOLA) ---------------------- *
+ * Input signal of a stream: its packed-sink output in the handle's format
+ * (any of the nine rates fs, C = out_channels 1 or 2, float32 interleaved):
+ * x_c[0 .. N) since the stream's last stretch restart, x outside [0, N) = 0.
+ * Sample windows and MP3D_PACK_GAPLESS act before it.
+ *
+ * Constants of the format: H = (fs + 50) / 100 in integer division (10 ms:
+ * 480 at 48 kHz, 80 at 8 kHz, 110 at 11 025 Hz); D = H / 2, the search radius.
+ *
+ * Tempo of a slot: a rational num / den, 1 <= num, den <= 4096 and
+ * 1/2 <= num/den <= 2.  The output plays num/den times as fast and has
+ * M = ceil(N den / num) samples per channel.
+ *
+ * Crossfade table: w[n] = float32(0.5 - 0.5 cos(pi (n + 0.5) / H)), n < H,
+ * computed in double (mp3d_stretch_window).
+ *
+ * Match signal, integers:
+ *   m[i] = x_0[i] (mono), 0.5f * (x_0[i] + x_1[i]) (stereo), float32
+ *   q[i] = (int) clamp(floorf(m[i] * 1024.0f + 0.5f), -1023, 1023)
+ * Samples are finite; a NaN gives an unspecified result but no fault.
+ *
+ * Block k = 0, 1, ... is output samples [kH, (k+1)H):
+ *   t_k = floor(k H num / den) (64-bit), t_{-1} = -H
+ *   a_{-1} = -H;  r_k = a_{k-1} + H (where the last segment would go on)
+ *   a_0 = 0;  for k >= 1, over every delta in [-D, D] with t_k + delta >= 0:
+ *     d_k(delta) = sum_{n<H} (q[r_k + n] - q[t_k + delta + n])^2
+ *   an exact integer that fits int32 (2046^2 * 480 < 2^31); delta_k is the
+ *   delta of the smallest d_k, ties to the smallest |delta|, then to the
+ *   negative one; a_k = t_k + delta_k
+ *   y_c[kH + n] = x_c[r_k + n] + fl(w[n] * fl(x_c[a_k + n] - x_c[r_k + n]))
+ * three separately rounded float32 operations, never fused.  Every term is
+ * exact or one rounding, so the output has one value whatever call or lane
+ * computes it.  At num == den every delta_k is 0 and y == x; a signal of an
+ * integer period P <= 2D comes out as the same periodic signal at any tempo
+ * wherever no block reads past N.
+ *
+ * Emit rule (data independent): block k is emitted once sample e_k has been
+ * seen (N - 1 >= e_k),
+ *   e_k = max(max(t_k, t_{k-1} + H) + D + H - 1, t_{k+1} - 1)
+ * the first term covers every sample a candidate or r_k can read (r_k <=
+ * t_{k-1} + D + H), the second keeps a whole emitted block inside M.
+ * MP3D_PACK_FLUSH also emits every block with kH < M, with zeros past N, the
+ * last block cut to M - kH samples: the lifetime total is exactly M; then the
+ * slot's stretch state restarts.
+ *
+ * Overflow: a stream whose call would emit more than out_stride samples gets
+ * count -1, writes nothing and restarts.  A call that feeds S samples emits at
+ * most mp3d_stretch_max_samples = ceil((S + 2H + D) den / num): the next block
+ * k before the call has N <= e_k, and with t_j <= jH num / den that gives
+ *   N den / num - kH <= max((D + H - 1) den / num,
+ *                           (2H + D - 1) den / num - H,  H) <= (2H + D) den / num
+ * (den / num >= 1/2), so no more than (S + 2H + D) den / num samples of the
+ * M after the call are still to be emitted.
+ *
+ * The per-slot stretch state (N, k, a_{k-1} and the input from max(0,
+ * min(r_k, t_k - D)) on, at most 3H + D - 1 sample frames) lives in the
+ * handle while stretch is set, not in the state blob.  It restarts where the
+ * true-peak state does: at create, at mp3d_batch_reset, at
+ * mp3d_batch_set_state on its slot, at mp3d_batch_set_output (which also
+ * turns stretch off), at mp3d_batch_set_stretch, at mp3d_batch_set_window on
+ * its slot, after its own flush and after an overflow; and at
+ * mp3d_batch_set_tempo on its slot.                                        */
+
+/* host only, no GPU: w[H] as defined above (NULL: size only); cap = floats w
+ * can hold; returns H, or MP3D_E_ARG for a rate that is not an MPEG audio
+ * rate or a short cap */
+MP3D_API long long mp3d_stretch_window(int hz, float *w, size_t cap);
+
+/* host only: an out_stride no stream can exceed in one call that feeds
+ * in_samples (at most 2^31 - 1) samples at tempo num / den, whatever earlier
+ * calls left pending and flushed or not: ceil((in_samples + 2H + D) den / num).
+ * MP3D_E_ARG for a bad rate, count or ratio. */
+MP3D_API long long mp3d_stretch_max_samples(int out_hz, long long in_samples, int num, int den);
+
+/* Needs a packed format (mp3d_batch_set_output), else MP3D_E_ARG.  on != 0
+ * uploads w, restarts every slot's stretch state, sets every slot's tempo to
+ * 1/1 and waits for the handle's work; on = 0 turns the sink off and frees its
+ * buffers. */
+MP3D_API int mp3d_batch_set_stretch(mp3d_batch *b, int on);
+
+/* The tempo of slots [first, first + n): num and den are host arrays.
+ * Restarts those slots' stretch state and waits for the handle's work.
+ * MP3D_E_ARG (nothing written) for a ratio outside the range above or before
+ * mp3d_batch_set_stretch; MP3D_E_CAPACITY past max_streams. */
+MP3D_API int mp3d_batch_set_tempo(mp3d_batch *b, int first, int n, const int *num, const int *den);
+
+/* The stage: feeds counts[s] (clamped to [0, sample_stride]) sample frames
+ * from samples + s * sample_stride * out_channels per stream through the
+ * slots' stretch state and writes the emitted blocks to out + s * out_stride *
+ * out_channels and their sample count to out_count[s] (-1: over out_stride).
+ * Nothing past out_count[s] is written.  samples, counts, out and out_count
+ * are host or device memory (a host samples array is read whole; a host out
+ * is filled by one copy per stream); the call is asynchronous when all four
+ * are device memory.  Device pointers must be element-aligned and a device out
+ * aligned to one sample frame, else MP3D_E_ARG; both strides are at most
+ * 2^31 - 1; out may not overlap samples (MP3D_E_ARG).  flags: MP3D_PACK_FLUSH
+ * only.  Runs on the device out and out_count of mp3d_batch_decode_packed
+ * (float32), or with n_streams = 1 on the device output of
+ * mp3d_batch_decode_long_packed (one stream is a chain of blocks: it runs on
+ * one compute unit).  Its device out and out_count are valid inputs to
+ * mp3d_batch_features, mp3d_batch_loudness, mp3d_batch_true_peak and
+ * mp3d_batch_apply_gain.  Leaves decoder, resampler, feature, loudness and
+ * true-peak state untouched.  MP3D_E_ARG before mp3d_batch_set_stretch.     */
+MP3D_API int mp3d_batch_stretch(mp3d_batch *b, const float *samples, long long sample_stride, const int *counts,
+                                int n_streams, float *out, long long out_stride, int *out_count, int flags,
+                                void *hip_stream);
+
+/* mp3d_batch_decode_packed (float32) into a handle-owned buffer of stride
+ * mp3d_packed_max_samples(out_hz, frames_per_stream, 0) with device counts,
+ * then the stage on them.  flags: MP3D_PACK_FLUSH | MP3D_PACK_GAPLESS, both
+ * forwarded (the flush ends the resampler, then the stretch).               */
+MP3D_API int mp3d_batch_decode_stretched(mp3d_batch *b, const uint8_t *frames, const uint64_t *offsets,
+                                         const uint32_t *sizes, int n_streams, int frames_per_stream, float *out,
+                                         long long out_stride, int *out_count, int flags, mp3d_frame_info *infos,
+                                         void *hip_stream);
+
+/* device-side microseconds of the stretch stage of the last stretch call
+ * (mp3d_batch_stretch, mp3d_batch_decode_stretched); needs
+ * mp3d_batch_set_timing */
+MP3D_API int mp3d_batch_stretch_time(mp3d_batch *b, float *us);
+
 /* ---- diagnostics -------------------------------------------------------- */
 MP3D_API const char *mp3d_strerror(int err);
 MP3D_API int mp3d_last_hip_error(void);

@@ -60,7 +60,9 @@ EXPORTS = ["mp3d_dec_create", "mp3d_dec_create_on", "mp3d_dec_destroy", "mp3d_de
            "mp3d_batch_loudness", "mp3d_batch_decode_loudness", "mp3d_loudness_integrated",
            "mp3d_batch_loudness_integrated", "mp3d_batch_loudness_time", "mp3d_truepeak_filter",
            "mp3d_batch_set_true_peak", "mp3d_batch_true_peak", "mp3d_batch_decode_measure",
-           "mp3d_batch_normalize_gain", "mp3d_batch_apply_gain", "mp3d_batch_true_peak_time"]
+           "mp3d_batch_normalize_gain", "mp3d_batch_apply_gain", "mp3d_batch_true_peak_time", "mp3d_stretch_window",
+           "mp3d_stretch_max_samples", "mp3d_batch_set_stretch", "mp3d_batch_set_tempo", "mp3d_batch_stretch",
+           "mp3d_batch_decode_stretched", "mp3d_batch_stretch_time"]
 
 OPT_CRC_CHECK = 1  # MP3D_OPT_CRC_CHECK: drop frames whose CRC-16 mismatches
 LONG_GAPLESS = 1  # MP3D_LONG_GAPLESS: apply the LAME tag's trim inside decode_long_packed
@@ -160,6 +162,16 @@ def _bind(L):
         L.mp3d_batch_normalize_gain.argtypes = [vp, vp, vp, i, ctypes.c_double, ctypes.c_double, vp, vp]
         L.mp3d_batch_apply_gain.argtypes = [vp, vp, ctypes.c_longlong, vp, i, vp, vp, i, vp]
         L.mp3d_batch_true_peak_time.argtypes = [vp, vp]
+    if hasattr(L, "mp3d_batch_set_stretch"):  # (an older build loaded for an A/B lacks the tempo sink)
+        L.mp3d_stretch_window.argtypes = [i, vp, ctypes.c_size_t]
+        L.mp3d_stretch_window.restype = ctypes.c_longlong
+        L.mp3d_stretch_max_samples.argtypes = [i, ctypes.c_longlong, i, i]
+        L.mp3d_stretch_max_samples.restype = ctypes.c_longlong
+        L.mp3d_batch_set_stretch.argtypes = [vp, i]
+        L.mp3d_batch_set_tempo.argtypes = [vp, i, i, vp, vp]
+        L.mp3d_batch_stretch.argtypes = [vp, vp, ctypes.c_longlong, vp, i, vp, ctypes.c_longlong, vp, i, vp]
+        L.mp3d_batch_decode_stretched.argtypes = [vp, vp, u64p, u32p, i, i, vp, ctypes.c_longlong, vp, i, vp, vp]
+        L.mp3d_batch_stretch_time.argtypes = [vp, vp]
     if hasattr(L, "mp3d_debug_wglds_probe"):  # libmp3d_wglds.so only (tests/test_gpu_wglds.py)
         L.mp3d_debug_wglds_probe.argtypes = [i, i, vp, i]
     return L
@@ -381,6 +393,7 @@ class BatchDecoder:
         self._mels = 0  # a change of the output format turns the feature sink off
         self._loud = False  # and the loudness sink
         self._tp = False  # and the true-peak tap
+        self._stretch = False  # and the tempo sink
 
     def decode_packed(self, frames, offsets, sizes, frames_per_stream, out=None, counts=None, infos=None, f32=True,
                       flush=False, stride=None, stream=None, gapless=False):
@@ -723,6 +736,88 @@ class BatchDecoder:
         self._ck(self._L.mp3d_batch_true_peak_time(self._h, ctypes.byref(t)))
         return float(t.value)
 
+    def set_stretch(self, on=True):
+        """Turn the tempo sink on or off (mp3d_batch_set_stretch): a
+        pitch-preserving time stretch of the packed output, whatever its
+        format.  Needs set_output.  Restarts every stream's stretch state and
+        sets every stream's tempo to 1/1."""
+        self._ck(self._L.mp3d_batch_set_stretch(self._h, int(bool(on))))
+        self._stretch = bool(on)
+
+    def set_tempo(self, num, den, first=0):
+        """The tempo num / den of streams first, first + 1 ...
+        (mp3d_batch_set_tempo): integers in [1, 4096] with 1/2 <= num/den <= 2,
+        scalars (one stream) or equally long sequences.  The output plays
+        num/den times as fast.  Restarts those streams' stretch state."""
+        num = np.ascontiguousarray(num, np.int32).reshape(-1)
+        den = np.ascontiguousarray(den, np.int32).reshape(-1)
+        if num.size != den.size:
+            raise ValueError("num / den length mismatch")
+        self._ck(self._L.mp3d_batch_set_tempo(self._h, int(first), num.size, num.ctypes.data, den.ctypes.data))
+
+    def _stretch_args(self, n, out, out_counts, stride, default_stride):
+        hz, ch = getattr(self, "_out", (0, 0))
+        if stride is None:  # (stretch off: the call fails with MP3D_E_ARG)
+            stride = int(out.shape[1]) if out is not None else default_stride(hz) if getattr(self, "_stretch", 0) else 1
+        stride = int(stride)
+        if out is None:
+            out = np.zeros((n, stride, ch), np.float32)
+        if out_counts is None:
+            out_counts = np.zeros(n, np.int32)
+        return out, out_counts, stride
+
+    def stretch(self, samples, counts, out=None, out_counts=None, flush=False, stride=None, stream=None):
+        """The tempo sink alone (mp3d_batch_stretch): samples float32
+        [n, sample_stride, channels] in the packed format, counts int32 [n]
+        sample frames per stream (both host arrays or device tensors), e.g.
+        the device out and counts of decode_packed.  out: None (allocate host)
+        or float32 array/tensor [n, stride, channels], not overlapping samples;
+        out_counts int32 [n].  stride defaults to out's, else to the bound
+        that cannot overflow at the slowest tempo.  flush=True emits the rest
+        of every stream and restarts it.  Returns (out, out_counts): stream s
+        holds out_counts[s] samples per channel (-1: over the stride)."""
+        n, ss = int(samples.shape[0]), int(samples.shape[1])
+        if not hasattr(counts, "data_ptr"):
+            counts = np.ascontiguousarray(counts, np.int32)
+        out, out_counts, stride = self._stretch_args(n, out, out_counts, stride,
+                                                     lambda hz: stretch_max_samples(hz, ss, 1, 2))
+        sp, k1 = _ptr(samples)
+        cp, k2 = _ptr(counts)
+        op, k3 = _ptr(out)
+        oc, k4 = _ptr(out_counts)
+        self._ck(self._L.mp3d_batch_stretch(self._h, sp if ss else None, ss, cp, n, op, stride, oc,
+                                            PACK_FLUSH if flush else 0, ctypes.c_void_p(stream) if stream else None))
+        return out, out_counts
+
+    def decode_stretched(self, frames, offsets, sizes, frames_per_stream, out=None, counts=None, infos=None,
+                         flush=False, stride=None, stream=None, gapless=False):
+        """Decode as decode_packed does (float32) and write every stream's
+        samples at its tempo (mp3d_batch_decode_stretched).  stride defaults to
+        out's, else to the bound that cannot overflow at the slowest tempo.
+        flush and gapless as in decode_packed; the flush also ends the
+        stretch.  Returns (out, counts, infos)."""
+        off, sz = self._geom(offsets, sizes)
+        n, F = off.size, int(frames_per_stream)
+        out, counts, stride = self._stretch_args(
+            n, out, counts, stride, lambda hz: stretch_max_samples(hz, packed_max_samples(hz, F), 1, 2))
+        if infos is None:
+            infos = np.zeros((n, F), FRAME_INFO_DT)
+        fp, k1 = _ptr(frames)
+        op, k2 = _ptr(out)
+        cp, k3 = _ptr(counts)
+        ip, k4 = _ptr(infos)
+        self._ck(self._L.mp3d_batch_decode_stretched(self._h, fp, off.ctypes.data, sz.ctypes.data, n, F, op, stride, cp,
+                                                     (PACK_FLUSH if flush else 0) | (PACK_GAPLESS if gapless else 0),
+                                                     ip, ctypes.c_void_p(stream) if stream else None))
+        return out, counts, infos
+
+    def stretch_time_us(self):
+        """Device-side microseconds of the stretch stage of the last stretch
+        call (after set_timing)."""
+        t = ctypes.c_float()
+        self._ck(self._L.mp3d_batch_stretch_time(self._h, ctypes.byref(t)))
+        return float(t.value)
+
     def decode_normalized(self, frames, offsets, sizes, frames_per_stream, target=-23.0, max_dbtp=-1.0, out=None,
                           f32=True, gapless=False):
         """Decode streams that are whole in this call and normalise them to
@@ -958,6 +1053,21 @@ def truepeak_filter():
     t = np.zeros((4, 12), np.float32)
     _check(lib().mp3d_truepeak_filter(t.ctypes.data, t.size))
     return t
+
+
+def stretch_window(hz):
+    """The tempo sink's crossfade table at rate hz (mp3d_stretch_window; no
+    GPU needed): float32 [H], H = (hz + 50) // 100."""
+    H = int(_check(lib().mp3d_stretch_window(int(hz), None, 0)))
+    w = np.zeros(H, np.float32)
+    _check(lib().mp3d_stretch_window(int(hz), w.ctypes.data, w.size))
+    return w
+
+
+def stretch_max_samples(hz, in_samples, num=1, den=2):
+    """Smallest stride of stretch that can never overflow for one call
+    feeding in_samples samples at tempo num / den (mp3d_stretch_max_samples)."""
+    return int(_check(lib().mp3d_stretch_max_samples(int(hz), int(in_samples), int(num), int(den))))
 
 
 def long_packed_bound(data, out_hz):

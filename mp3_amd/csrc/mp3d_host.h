@@ -1,7 +1,7 @@
 /*
  * mp3d_host.h -- private to the host sources (mp3d_host_tables.cpp,
  * mp3d_batch.cpp, mp3d_long.cpp, mp3d_dec.cpp, mp3d_sinks.cpp,
- * mp3d_loudness.cpp, mp3d_normalize.cpp): the error
+ * mp3d_loudness.cpp, mp3d_normalize.cpp, mp3d_stretch.cpp): the error
  * macro, the owning device buffer, the batch handle and the internal
  * functions that cross those files.  Nothing here is exported (the library
  * is built with hidden visibility; the C ABI is include/mp3d.h).
@@ -27,6 +27,7 @@
 #include "mp3d_features.h"
 #include "mp3d_loudness.h"
 #include "mp3d_normalize.h"
+#include "mp3d_stretch.h"
 #include "mp3d_launch.h"
 
 namespace mp3d {
@@ -278,6 +279,28 @@ struct mp3d_batch {
             out.release();
         }
     } nm;
+    /* tempo sink (mp3d_batch_set_stretch; mp3d_stretch.h): on = false is off,
+     * and then none of these buffers exists.  st, plan, tempo (num, den per
+     * slot; it outlives a restart of st), cin and cnt hold max_streams
+     * entries; smp (a host caller's samples, or the packed samples of
+     * mp3d_batch_decode_stretched) and out (staging for a host sink) grow with
+     * the calls. */
+    struct StretchSink {
+        bool on = false;
+        int H = 0;
+        mp3d::DevBuf<float> w;
+        mp3d::DevBuf<StState> st;
+        mp3d::DevBuf<StPlan> plan;
+        mp3d::DevBuf<int32_t> tempo, cin, cnt;
+        mp3d::DevBuf<float> smp, out;
+        mp3d::StageTimer tm;
+        void off() {
+            w.release(), st.release(), plan.release(), tempo.release(), cin.release(), cnt.release(), smp.release();
+            out.release();
+            on = false, H = 0;
+            tm.timed = false;
+        }
+    } sx;
 };
 
 namespace mp3d {

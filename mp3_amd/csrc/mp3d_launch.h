@@ -10,12 +10,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-/* (layouts: mp3d_internal.h, mp3d_resample.h, mp3d_features.h, mp3d_loudness.h, mp3d_normalize.h) */
+/* (layouts: mp3d_internal.h, mp3d_resample.h, mp3d_features.h, mp3d_loudness.h, mp3d_normalize.h,
+ * mp3d_stretch.h) */
 struct StreamState; struct FrameRec; struct UnitMeta; struct DevTables;
 struct RsState; struct RsCfg; struct RsPlan; struct RsLong;
 struct FtState; struct FtPlan; struct FtTab;
 struct LdState; struct LdPlan; struct LdTab;
 struct TpState; struct TpPlan;
+struct StState; struct StPlan;
 
 namespace mp3d {
 
@@ -107,6 +109,12 @@ void launch_gain_calc(const float *lufs, const float *tpeak, float *gain, int n,
 /* k_gain_apply: packed float32 samples times their stream's gain, as float32 or int16; ccnt: the clamped counts */
 void launch_gain_apply(const float *samples, const int32_t *counts, const float *gain, void *out, int32_t *ccnt,
                        bool f32, int ch, int n, long long sample_stride, int chunks, hipStream_t strm);
+
+/* ---- mp3d_stretch.hip ---- */
+/* k_st_plan + k_st_blocks: packed float32 samples to the same signal at each stream's tempo (num, den pairs) */
+void launch_stretch(const float *samples, const int32_t *counts, StState *st, const int32_t *tempo, StPlan *plan,
+                    const float *w, float *out, int32_t *out_count, int n, long long sample_stride,
+                    long long out_stride, int H, int ch, int flush, hipStream_t strm);
 
 } // namespace mp3d
 

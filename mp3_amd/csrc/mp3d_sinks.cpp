@@ -161,6 +161,7 @@ extern "C" int mp3d_batch_set_output(mp3d_batch *b, int out_hz, int out_channels
     b->ft.off(); /* the feature sink reads this sink's format: off with any change of it */
     b->ld.off(); /* and so does the loudness sink */
     b->nm.off(); /* and the true-peak tap and the gain calls */
+    b->sx.off(); /* and the tempo sink */
     mp3d_batch::PackedSink &k = b->rs;
     if (out_hz == 0) {
         k.off();
@@ -275,6 +276,7 @@ extern "C" int mp3d_batch_set_window(mp3d_batch *b, int first, int n, const long
     if (b->ft.st) HIPCHK(hipMemsetAsync(b->ft.st + first, 0, sizeof(FtState) * (size_t)n, s));
     if (b->ld.st) HIPCHK(hipMemsetAsync(b->ld.st + first, 0, sizeof(LdState) * (size_t)n, s));
     if (b->nm.st) HIPCHK(hipMemsetAsync(b->nm.st + first, 0, sizeof(TpState) * (size_t)n, s));
+    if (b->sx.st) HIPCHK(hipMemsetAsync(b->sx.st + first, 0, sizeof(StState) * (size_t)n, s));
     if (lo)
         HIPCHK(hipMemcpy2DAsync(b->rs.st + first, sizeof(RsState), w.data(), sizeof(RsWindow), sizeof(RsWindow), (size_t)n,
                                 hipMemcpyHostToDevice, s));
