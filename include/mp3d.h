@@ -850,6 +850,125 @@ MP3D_API int mp3d_batch_decode_stretched(mp3d_batch *b, const uint8_t *frames, c
  * mp3d_batch_set_timing */
 MP3D_API int mp3d_batch_stretch_time(mp3d_batch *b, float *us);
 
+/* ---- limiter (look-ahead, true-peak detector) ------------------------------- *
+ * A per-sample gain stage behind the static gain of the normalise path: the
+ * gain may reach its loudness target (mp3d_batch_normalize_gain with tpeak =
+ * NULL) and the limiter holds the peaks under a ceiling.
+ *
+ * Input signal of a slot: packed-sink output in the handle's format (any of
+ * the nine rates fs, C = out_channels 1 or 2, float32 interleaved):
+ * x_c[0 .. N) since the slot's last limiter restart.  Samples are finite; a
+ * NaN or Inf gives an unspecified value but no fault.
+ *
+ * Constants: A = (fs + 50) / 100 in integer division, the look-ahead (10 ms:
+ * 480 at 48 kHz, 80 at 8 kHz, 110 at 11 025 Hz); Hd = 2A, the hold; Q = 2^20;
+ * the ceiling c = float32(10^(ceiling_db / 20)) computed in double,
+ * -20 <= ceiling_db <= 0, one per handle.
+ *
+ * Pre-gain: v_c[i] = fl(x_c[i] * gain[s]), one float32 multiply with the
+ * gain[s] of the call that fed sample i; a NULL gain is 1 and v is x itself;
+ * v outside [0, N) = 0.
+ *
+ * Detector: the true-peak tap's oversampler on v.  u_c[4i + p] exactly as in
+ * "true peak and gain" above (mp3d_truepeak_filter's taps, one float32 fmaf
+ * chain in ascending j from 0, phase 0 is |v|);
+ *   p[i] = max over c and p of |u_c[4i + p]|
+ *
+ * Required gain, integers from here on:
+ *   r[i] = 1 if p[i] <= c, else fl(c / p[i])         (IEEE float32 division)
+ *   R[i] = (int) floorf(r[i] * 1048576.0f)           (exact); R outside [0, N) = Q
+ *   m[k] = min_{k - Hd <= j <= k + A} R[j]
+ *   S[i] = sum_{j = 0 .. A} m[i - j]                 (fits int32: 481 * 2^20 < 2^31)
+ *   G[i] = S[i] / (A + 1)                            (integer division)
+ *   g[i] = (float) G[i] * 2^-20                      (exact)
+ *   y_c[i] = fl(v_c[i] * g[i])
+ * int16 output is the packed sink's clamp(floor(y * 32768 + 0.5)).
+ *
+ * What follows from it:
+ *   - every m[i - j] of the sum covers index i, so g[i] <= R[i] / Q <= r[i] and
+ *     |y_c[i]| <= c (1 + 2^-22) for every sample;
+ *   - if p[i] <= c over a whole stream, every g is 1 and y == v bit for bit;
+ *   - a peak at i0 pulls the gain down linearly over the A samples before it,
+ *     holds it for Hd samples and releases it over A + 1;
+ *   - the minimum and the sum are integers: any evaluation order, tile size or
+ *     scan gives the same G, and any split of a stream into calls the same y;
+ *   - the TRUE peak of y is not bounded by c exactly, because the gain moves
+ *     between samples: it is measured, not promised.
+ *
+ * Emit rule: sample i is emitted once sample i + A + 6 has been seen.
+ * MP3D_PACK_FLUSH also emits every i < N, with zeros past N, then restarts the
+ * slot.  A slot's lifetime output count equals its input count.  A call that
+ * feeds S samples emits at most S + A + 6 (mp3d_limiter_max_samples).  A
+ * stream whose call would emit more than out_stride gets count -1, writes
+ * nothing and restarts.
+ *
+ * gr[s] (optional) = the minimum g[i] over the samples the call emits, float32
+ * and exact; 1 when it emits none.  A caller folds a stream's calls with min.
+ *
+ * Emitting i reads v[i - 3A - 5 .. i + A + 6]: the per-slot limiter state is a
+ * sample count and the last 4A + 11 sample frames of v (15 456 bytes at 48 kHz
+ * stereo).  It lives in the handle while the limiter is set, not in the state
+ * blob, and restarts where the true-peak state does: at create, at
+ * mp3d_batch_reset, at mp3d_batch_set_state on its slot, at
+ * mp3d_batch_set_output (which also turns the limiter off), at
+ * mp3d_batch_set_limiter, at mp3d_batch_set_window on its slot, after its own
+ * flush and after an overflow.                                               */
+
+/* host only: A at rate hz, or MP3D_E_ARG for a rate that is not an MPEG audio
+ * rate */
+MP3D_API long long mp3d_limiter_lookahead(int hz);
+
+/* host only: an out_stride no stream can exceed in one call that feeds
+ * in_samples (at most 2^31 - 1) samples, whatever earlier calls left pending
+ * and flushed or not: in_samples + A + 6.  MP3D_E_ARG for a bad rate or count. */
+MP3D_API long long mp3d_limiter_max_samples(int hz, long long in_samples);
+
+/* Needs a packed format (mp3d_batch_set_output) and -20 <= ceiling_db <= 0,
+ * else MP3D_E_ARG.  on != 0 sets the ceiling, restarts every slot's limiter
+ * state and waits for the handle's work; on = 0 turns the limiter off and
+ * frees its buffers. */
+MP3D_API int mp3d_batch_set_limiter(mp3d_batch *b, int on, double ceiling_db);
+
+/* The stage: feeds counts[s] (clamped to [0, sample_stride]) sample frames
+ * from samples + s * sample_stride * out_channels per stream, times gain[s]
+ * (gain NULL: 1), through the slots' limiter state and writes the emitted
+ * samples as float32 (f32 != 0) or int16 to out + s * out_stride *
+ * out_channels elements, their count to out_count[s] (-1: over out_stride)
+ * and, when gr is not NULL, the call's smallest gain to gr[s].  Nothing past
+ * out_count[s] is written.  samples, counts, gain, out, out_count and gr are
+ * host or device memory (a host samples array is read whole; a host out is
+ * filled by one copy per stream); the call is asynchronous when all of them
+ * are device memory.  Device pointers must be element-aligned and a device out
+ * aligned to one sample frame, else MP3D_E_ARG; both strides are at most
+ * 2^31 - 1 - 8192 frames, and n_streams * ceil(min(sample_stride + A + 6,
+ * out_stride) / 4096) at most (2^32 - 1) / 384, the launch's size, else
+ * MP3D_E_CAPACITY; out may not overlap samples (MP3D_E_ARG).  flags:
+ * MP3D_PACK_FLUSH only.  Runs on the device out and out_count of
+ * mp3d_batch_decode_packed (float32), or with n_streams = 1 on the device
+ * output of mp3d_batch_decode_long_packed: tiles are independent, so one long
+ * stream is spread over the whole GPU.  Its float32 device out and out_count
+ * are valid inputs to mp3d_batch_features, mp3d_batch_loudness,
+ * mp3d_batch_true_peak and mp3d_batch_apply_gain.  Leaves decoder, resampler,
+ * feature, loudness, true-peak and stretch state untouched.  MP3D_E_ARG before
+ * mp3d_batch_set_limiter.                                                    */
+MP3D_API int mp3d_batch_limit(mp3d_batch *b, const float *samples, long long sample_stride, const int *counts,
+                              int n_streams, const float *gain, void *out, int f32, long long out_stride,
+                              int *out_count, float *gr, int flags, void *hip_stream);
+
+/* mp3d_batch_decode_packed (float32) into a handle-owned buffer of stride
+ * mp3d_packed_max_samples(out_hz, frames_per_stream, 0) with device counts,
+ * then the stage on them with gain, out, f32, out_stride, out_count and gr as
+ * above.  flags: MP3D_PACK_FLUSH | MP3D_PACK_GAPLESS, both forwarded (the
+ * flush ends the resampler, then the limiter).                              */
+MP3D_API int mp3d_batch_decode_limited(mp3d_batch *b, const uint8_t *frames, const uint64_t *offsets,
+                                       const uint32_t *sizes, int n_streams, int frames_per_stream, const float *gain,
+                                       void *out, int f32, long long out_stride, int *out_count, float *gr, int flags,
+                                       mp3d_frame_info *infos, void *hip_stream);
+
+/* device-side microseconds of the limiter stage of the last limiter call
+ * (mp3d_batch_limit, mp3d_batch_decode_limited); needs mp3d_batch_set_timing */
+MP3D_API int mp3d_batch_limiter_time(mp3d_batch *b, float *us);
+
 /* ---- diagnostics -------------------------------------------------------- */
 MP3D_API const char *mp3d_strerror(int err);
 MP3D_API int mp3d_last_hip_error(void);

@@ -62,7 +62,9 @@ EXPORTS = ["mp3d_dec_create", "mp3d_dec_create_on", "mp3d_dec_destroy", "mp3d_de
            "mp3d_batch_set_true_peak", "mp3d_batch_true_peak", "mp3d_batch_decode_measure",
            "mp3d_batch_normalize_gain", "mp3d_batch_apply_gain", "mp3d_batch_true_peak_time", "mp3d_stretch_window",
            "mp3d_stretch_max_samples", "mp3d_batch_set_stretch", "mp3d_batch_set_tempo", "mp3d_batch_stretch",
-           "mp3d_batch_decode_stretched", "mp3d_batch_stretch_time"]
+           "mp3d_batch_decode_stretched", "mp3d_batch_stretch_time", "mp3d_limiter_lookahead",
+           "mp3d_limiter_max_samples", "mp3d_batch_set_limiter", "mp3d_batch_limit", "mp3d_batch_decode_limited",
+           "mp3d_batch_limiter_time"]
 
 OPT_CRC_CHECK = 1  # MP3D_OPT_CRC_CHECK: drop frames whose CRC-16 mismatches
 LONG_GAPLESS = 1  # MP3D_LONG_GAPLESS: apply the LAME tag's trim inside decode_long_packed
@@ -172,6 +174,16 @@ def _bind(L):
         L.mp3d_batch_stretch.argtypes = [vp, vp, ctypes.c_longlong, vp, i, vp, ctypes.c_longlong, vp, i, vp]
         L.mp3d_batch_decode_stretched.argtypes = [vp, vp, u64p, u32p, i, i, vp, ctypes.c_longlong, vp, i, vp, vp]
         L.mp3d_batch_stretch_time.argtypes = [vp, vp]
+    if hasattr(L, "mp3d_batch_set_limiter"):  # (an older build loaded for an A/B lacks the limiter)
+        L.mp3d_limiter_lookahead.argtypes = [i]
+        L.mp3d_limiter_lookahead.restype = ctypes.c_longlong
+        L.mp3d_limiter_max_samples.argtypes = [i, ctypes.c_longlong]
+        L.mp3d_limiter_max_samples.restype = ctypes.c_longlong
+        L.mp3d_batch_set_limiter.argtypes = [vp, i, ctypes.c_double]
+        L.mp3d_batch_limit.argtypes = [vp, vp, ctypes.c_longlong, vp, i, vp, vp, i, ctypes.c_longlong, vp, vp, i, vp]
+        L.mp3d_batch_decode_limited.argtypes = [vp, vp, u64p, u32p, i, i, vp, vp, i, ctypes.c_longlong, vp, vp, i, vp,
+                                                vp]
+        L.mp3d_batch_limiter_time.argtypes = [vp, vp]
     if hasattr(L, "mp3d_debug_wglds_probe"):  # libmp3d_wglds.so only (tests/test_gpu_wglds.py)
         L.mp3d_debug_wglds_probe.argtypes = [i, i, vp, i]
     return L
@@ -394,6 +406,7 @@ class BatchDecoder:
         self._loud = False  # and the loudness sink
         self._tp = False  # and the true-peak tap
         self._stretch = False  # and the tempo sink
+        self._limit = None  # and the limiter (its ceiling in dBTP while it is on)
 
     def decode_packed(self, frames, offsets, sizes, frames_per_stream, out=None, counts=None, infos=None, f32=True,
                       flush=False, stride=None, stream=None, gapless=False):
@@ -818,19 +831,114 @@ class BatchDecoder:
         self._ck(self._L.mp3d_batch_stretch_time(self._h, ctypes.byref(t)))
         return float(t.value)
 
+    def set_limiter(self, on=True, ceiling_db=-1.0):
+        """Turn the look-ahead true-peak limiter on or off
+        (mp3d_batch_set_limiter): a per-sample gain on the packed output,
+        whatever its format, that holds the 4x oversampled peak of every sample
+        frame at or below ceiling_db dBTP (-20 .. 0).  Needs set_output.
+        Restarts every stream's limiter state."""
+        self._ck(self._L.mp3d_batch_set_limiter(self._h, int(bool(on)), float(ceiling_db)))
+        self._limit = float(ceiling_db) if on else None
+
+    def _limit_args(self, n, out, out_counts, gain, gr, f32, stride, default_stride):
+        hz, ch = getattr(self, "_out", (0, 0))
+        if stride is None:  # (limiter off: the call fails with MP3D_E_ARG)
+            on = getattr(self, "_limit", None) is not None
+            stride = int(out.shape[1]) if out is not None else default_stride(hz) if on else 1
+        stride = int(stride)
+        if out is None:
+            out = np.zeros((n, stride, ch), np.float32 if f32 else np.int16)
+        if out_counts is None:
+            out_counts = np.zeros(n, np.int32)
+        if gain is not None and not hasattr(gain, "data_ptr"):
+            gain = np.ascontiguousarray(gain, np.float32)
+        if gr is None:
+            gr = np.ones(n, np.float32)
+        return out, out_counts, gain, gr, stride
+
+    def limit(self, samples, counts, gain=None, out=None, out_counts=None, gr=None, f32=True, flush=False, stride=None,
+              stream=None):
+        """The limiter alone (mp3d_batch_limit): samples float32
+        [n, sample_stride, channels] in the packed format, counts int32 [n]
+        sample frames per stream (both host arrays or device tensors), e.g.
+        the device out and counts of decode_packed; gain float32 [n], applied
+        before the limiter (None: 1).  out: None (allocate host) or float32
+        (int16 with f32=False) array/tensor [n, stride, channels], not
+        overlapping samples; out_counts int32 [n]; gr float32 [n] receives the
+        smallest gain of the call per stream.  stride defaults to out's, else
+        to the bound that cannot overflow.  flush=True emits the last A + 6
+        samples of every stream and restarts it.  Returns (out, out_counts,
+        gr): stream s holds out_counts[s] samples per channel (-1: over the
+        stride)."""
+        n, ss = int(samples.shape[0]), int(samples.shape[1])
+        if not hasattr(counts, "data_ptr"):
+            counts = np.ascontiguousarray(counts, np.int32)
+        out, out_counts, gain, gr, stride = self._limit_args(n, out, out_counts, gain, gr, f32, stride,
+                                                             lambda hz: limiter_max_samples(hz, ss))
+        sp, k1 = _ptr(samples)
+        cp, k2 = _ptr(counts)
+        gp, k3 = _ptr(gain)
+        op, k4 = _ptr(out)
+        oc, k5 = _ptr(out_counts)
+        rp, k6 = _ptr(gr)
+        self._ck(self._L.mp3d_batch_limit(self._h, sp if ss else None, ss, cp, n, gp, op, int(bool(f32)), stride, oc, rp,
+                                          PACK_FLUSH if flush else 0, ctypes.c_void_p(stream) if stream else None))
+        return out, out_counts, gr
+
+    def decode_limited(self, frames, offsets, sizes, frames_per_stream, gain=None, out=None, counts=None, gr=None,
+                       infos=None, f32=True, flush=False, stride=None, stream=None, gapless=False):
+        """Decode as decode_packed does (float32) and write every stream's
+        samples times gain through the limiter (mp3d_batch_decode_limited).
+        stride defaults to out's, else to the bound that cannot overflow.
+        flush and gapless as in decode_packed; the flush also ends the
+        limiter.  Returns (out, counts, gr, infos)."""
+        off, sz = self._geom(offsets, sizes)
+        n, F = off.size, int(frames_per_stream)
+        out, counts, gain, gr, stride = self._limit_args(
+            n, out, counts, gain, gr, f32, stride, lambda hz: limiter_max_samples(hz, packed_max_samples(hz, F)))
+        if infos is None:
+            infos = np.zeros((n, F), FRAME_INFO_DT)
+        fp, k1 = _ptr(frames)
+        gp, k2 = _ptr(gain)
+        op, k3 = _ptr(out)
+        cp, k4 = _ptr(counts)
+        rp, k5 = _ptr(gr)
+        ip, k6 = _ptr(infos)
+        self._ck(self._L.mp3d_batch_decode_limited(self._h, fp, off.ctypes.data, sz.ctypes.data, n, F, gp, op,
+                                                   int(bool(f32)), stride, cp, rp,
+                                                   (PACK_FLUSH if flush else 0) | (PACK_GAPLESS if gapless else 0), ip,
+                                                   ctypes.c_void_p(stream) if stream else None))
+        return out, counts, gr, infos
+
+    def limiter_time_us(self):
+        """Device-side microseconds of the limiter stage of the last limiter
+        call (after set_timing)."""
+        t = ctypes.c_float()
+        self._ck(self._L.mp3d_batch_limiter_time(self._h, ctypes.byref(t)))
+        return float(t.value)
+
     def decode_normalized(self, frames, offsets, sizes, frames_per_stream, target=-23.0, max_dbtp=-1.0, out=None,
-                          f32=True, gapless=False):
+                          f32=True, gapless=False, limit=False):
         """Decode streams that are whole in this call and normalise them to
         target LUFS under max_dbtp dBTP, all on the device with no host sync
         between the stages: decode_packed(flush), loudness(flush),
         true_peak(flush), integrated_lufs, normalize_gain, apply_gain.  Needs
         set_loudness and set_true_peak.  out: None (allocate host) or float32
         (int16 with f32=False) array/tensor [n, packed_max_samples, channels].
+        limit=True (needs set_limiter with ceiling_db == max_dbtp): the gain
+        is not capped by the true peak, so every stream reaches the target,
+        and the limiter takes the place of apply_gain and holds the peaks
+        under the ceiling; tpeak stays the measurement before it.
         Returns (out, counts, lufs, tpeak, gain, infos): out as given, the rest
         host arrays."""
         import torch
         if not (getattr(self, "_loud", False) and getattr(self, "_tp", False)):
             raise MP3DError("decode_normalized needs set_loudness and set_true_peak")
+        if limit:
+            if getattr(self, "_limit", None) is None:
+                raise MP3DError("decode_normalized(limit=True) needs set_limiter")
+            if float(max_dbtp) != self._limit:
+                raise MP3DError("max_dbtp %r is not the limiter's ceiling %r" % (max_dbtp, self._limit))
         off, sz = self._geom(offsets, sizes)
         n, F = off.size, int(frames_per_stream)
         hz, ch = self._out
@@ -851,8 +959,13 @@ class BatchDecoder:
         self.loudness(smp, counts, blocks=blocks, block_counts=bc, peak=peak, flush=True)
         self.true_peak(smp, counts, tpeak=tpeak, flush=True)
         self.integrated_lufs(blocks, bc, lufs=lufs)
-        self.normalize_gain(lufs, tpeak, target=target, max_dbtp=max_dbtp, gain=gain)
-        self.apply_gain(smp, counts, gain, out=out, f32=f32)
+        if limit:
+            self.normalize_gain(lufs, None, target=target, max_dbtp=max_dbtp, gain=gain)
+            oc, gr = torch.empty((n,), dtype=torch.int32, device=dev), torch.empty((n,), dtype=torch.float32, device=dev)
+            self.limit(smp, counts, gain, out=out, out_counts=oc, gr=gr, f32=f32, flush=True)
+        else:
+            self.normalize_gain(lufs, tpeak, target=target, max_dbtp=max_dbtp, gain=gain)
+            self.apply_gain(smp, counts, gain, out=out, f32=f32)
         self.sync()
         infos = infos.cpu().numpy().view(FRAME_INFO_DT).reshape(n, F)
         return out, counts.cpu().numpy(), lufs.cpu().numpy(), tpeak.cpu().numpy(), gain.cpu().numpy(), infos
@@ -1068,6 +1181,18 @@ def stretch_max_samples(hz, in_samples, num=1, den=2):
     """Smallest stride of stretch that can never overflow for one call
     feeding in_samples samples at tempo num / den (mp3d_stretch_max_samples)."""
     return int(_check(lib().mp3d_stretch_max_samples(int(hz), int(in_samples), int(num), int(den))))
+
+
+def limiter_lookahead(hz):
+    """The limiter's look-ahead A = (hz + 50) // 100 in samples at rate hz
+    (mp3d_limiter_lookahead; no GPU needed)."""
+    return int(_check(lib().mp3d_limiter_lookahead(int(hz))))
+
+
+def limiter_max_samples(hz, in_samples):
+    """Smallest stride of limit that can never overflow for one call feeding
+    in_samples samples (mp3d_limiter_max_samples): in_samples + A + 6."""
+    return int(_check(lib().mp3d_limiter_max_samples(int(hz), int(in_samples))))
 
 
 def long_packed_bound(data, out_hz):

@@ -131,7 +131,7 @@ extern "C" int mp3d_batch_create(int device, int max_streams, int max_frames, mp
         return MP3D_E_HIP;
     }
     for (auto &e : b->ev) (void)hipEventCreate(&e);
-    for (StageTimer *t : {&b->rs.tm, &b->ft.tm, &b->ld.tm, &b->nm.tm, &b->sx.tm})
+    for (StageTimer *t : {&b->rs.tm, &b->ft.tm, &b->ld.tm, &b->nm.tm, &b->sx.tm, &b->lm.tm})
         for (auto &e : t->ev) (void)hipEventCreate(&e);
     r = b->st_mem.grow(b, sizeof(StreamState) * ns);
     if (!r) r = b->rec.grow(b, sizeof(FrameRec) * fr);
@@ -179,7 +179,7 @@ extern "C" void mp3d_batch_destroy(mp3d_batch *b) {
     }
     for (hipEvent_t e : b->ev)
         if (e) (void)hipEventDestroy(e);
-    for (StageTimer *t : {&b->rs.tm, &b->ft.tm, &b->ld.tm, &b->nm.tm, &b->sx.tm})
+    for (StageTimer *t : {&b->rs.tm, &b->ft.tm, &b->ld.tm, &b->nm.tm, &b->sx.tm, &b->lm.tm})
         for (hipEvent_t e : t->ev)
             if (e) (void)hipEventDestroy(e);
     if (b->ev_done) (void)hipEventDestroy(b->ev_done);
@@ -200,6 +200,7 @@ extern "C" int mp3d_batch_reset(mp3d_batch *b) {
     if (b->ld.st) HIPCHK(hipMemsetAsync(b->ld.st, 0, sizeof(LdState) * (size_t)b->max_streams, b->own));
     if (b->nm.st) HIPCHK(hipMemsetAsync(b->nm.st, 0, sizeof(TpState) * (size_t)b->max_streams, b->own));
     if (b->sx.st) HIPCHK(hipMemsetAsync(b->sx.st, 0, sizeof(StState) * (size_t)b->max_streams, b->own));
+    if (b->lm.st) HIPCHK(hipMemsetAsync(b->lm.st, 0, sizeof(LimState) * (size_t)b->max_streams, b->own));
     HIPCHK(hipStreamSynchronize(b->own));
     return MP3D_OK;
 }
@@ -657,6 +658,7 @@ static int state_copy(mp3d_batch *b, int first, int n, void *dst, const void *sr
     if (!out && b->ld.st) HIPCHK(hipMemsetAsync(b->ld.st + first, 0, sizeof(LdState) * (size_t)n, s));
     if (!out && b->nm.st) HIPCHK(hipMemsetAsync(b->nm.st + first, 0, sizeof(TpState) * (size_t)n, s));
     if (!out && b->sx.st) HIPCHK(hipMemsetAsync(b->sx.st + first, 0, sizeof(StState) * (size_t)n, s));
+    if (!out && b->lm.st) HIPCHK(hipMemsetAsync(b->lm.st + first, 0, sizeof(LimState) * (size_t)n, s));
     HIPCHK(hipStreamSynchronize(s));
     return MP3D_OK;
 }

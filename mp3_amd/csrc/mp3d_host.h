@@ -1,7 +1,7 @@
 /*
  * mp3d_host.h -- private to the host sources (mp3d_host_tables.cpp,
  * mp3d_batch.cpp, mp3d_long.cpp, mp3d_dec.cpp, mp3d_sinks.cpp,
- * mp3d_loudness.cpp, mp3d_normalize.cpp, mp3d_stretch.cpp): the error
+ * mp3d_loudness.cpp, mp3d_normalize.cpp, mp3d_stretch.cpp, mp3d_limiter.cpp): the error
  * macro, the owning device buffer, the batch handle and the internal
  * functions that cross those files.  Nothing here is exported (the library
  * is built with hidden visibility; the C ABI is include/mp3d.h).
@@ -28,6 +28,7 @@
 #include "mp3d_loudness.h"
 #include "mp3d_normalize.h"
 #include "mp3d_stretch.h"
+#include "mp3d_limiter.h"
 #include "mp3d_launch.h"
 
 namespace mp3d {
@@ -301,6 +302,30 @@ struct mp3d_batch {
             tm.timed = false;
         }
     } sx;
+    /* limiter (mp3d_batch_set_limiter; mp3d_limiter.h): on = false is off, and
+     * then none of these buffers exists.  taps, st, plan, cin, cnt, gg (a host
+     * caller's gains) and grd (gr for a host caller) hold max_streams entries;
+     * smp (a host caller's samples, or the packed samples of
+     * mp3d_batch_decode_limited), out (staging for a host sink) and the
+     * per-tile scratch tile grow with the calls. */
+    struct LimiterSink {
+        bool on = false;
+        int A = 0;
+        float c = 1.0f; /* the ceiling, linear */
+        mp3d::DevBuf<float> taps;
+        mp3d::DevBuf<LimState> st;
+        mp3d::DevBuf<LimPlan> plan;
+        mp3d::DevBuf<int32_t> cin, cnt;
+        mp3d::DevBuf<float> smp, gg, grd, tile;
+        mp3d::DevBuf<void> out;
+        mp3d::StageTimer tm;
+        void off() {
+            taps.release(), st.release(), plan.release(), cin.release(), cnt.release(), smp.release(), gg.release();
+            grd.release(), tile.release(), out.release();
+            on = false, A = 0, c = 1.0f;
+            tm.timed = false;
+        }
+    } lm;
 };
 
 namespace mp3d {

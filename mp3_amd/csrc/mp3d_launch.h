@@ -11,13 +11,14 @@
 #include <stdint.h>
 
 /* (layouts: mp3d_internal.h, mp3d_resample.h, mp3d_features.h, mp3d_loudness.h, mp3d_normalize.h,
- * mp3d_stretch.h) */
+ * mp3d_stretch.h, mp3d_limiter.h) */
 struct StreamState; struct FrameRec; struct UnitMeta; struct DevTables;
 struct RsState; struct RsCfg; struct RsPlan; struct RsLong;
 struct FtState; struct FtPlan; struct FtTab;
 struct LdState; struct LdPlan; struct LdTab;
 struct TpState; struct TpPlan;
 struct StState; struct StPlan;
+struct LimState; struct LimPlan;
 
 namespace mp3d {
 
@@ -115,6 +116,14 @@ void launch_gain_apply(const float *samples, const int32_t *counts, const float 
 void launch_stretch(const float *samples, const int32_t *counts, StState *st, const int32_t *tempo, StPlan *plan,
                     const float *w, float *out, int32_t *out_count, int n, long long sample_stride,
                     long long out_stride, int H, int ch, int flush, hipStream_t strm);
+
+/* ---- mp3d_limiter.hip ---- */
+/* k_lim_plan + k_lim_tile + k_lim_carry: packed float32 samples times gain[s] (null: 1) and the limiter's gain
+ * envelope under the ceiling c to float32 or int16; tilemin holds n * tiles floats, gr may be null */
+void launch_limiter(const float *samples, const int32_t *counts, LimState *st, LimPlan *plan, const float *taps,
+                    const float *gain, void *out, int32_t *out_count, float *tilemin, float *gr, bool f32, int ch, int n,
+                    long long sample_stride, long long out_stride, int tiles, int A, float c, int flush,
+                    hipStream_t strm);
 
 } // namespace mp3d
 

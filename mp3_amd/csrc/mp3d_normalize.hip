@@ -27,6 +27,7 @@
  */
 #include "mp3d_device.h"
 #include "mp3d_normalize.h"
+#include "mp3d_tp_chain.h"
 #include "mp3d_launch.h"
 
 /* the wglds build and the product build must round alike: no implicit
@@ -62,30 +63,6 @@ k_tp_plan(const TpState *__restrict__ st, const int32_t *__restrict__ counts, Tp
     P.tiles = (P.n_emit + MP3D_TP_TILE - 1) / MP3D_TP_TILE;
     P.restart = flush;
     plan[s] = P;
-}
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-/* One sample frame (all its channels) as the unit of the filter: a float, or
- * a pair whose halves go through the same operations side by side. */
-template <int C> struct TpFrame;
-template <> struct TpFrame<1> {
-    typedef float T;
-    static __device__ __forceinline__ T bc(float c) { return c; }
-    static __device__ __forceinline__ T fma(T a, T b, T c) { return fmaf(a, b, c); }
-    static __device__ __forceinline__ float amax(T v) { return fabsf(v); }
-};
-template <> struct TpFrame<2> {
-    typedef f32x2 T;
-    static __device__ __forceinline__ T bc(float c) { return (f32x2){c, c}; }
-    static __device__ __forceinline__ T fma(T a, T b, T c) { return __builtin_elementwise_fma(a, b, c); }
-    static __device__ __forceinline__ float amax(T v) { return fmaxf(fabsf(v.x), fabsf(v.y)); }
-};
-
-/* element e of a span's interleaved samples to its frame's place in the padded runs */
-template <int C> __device__ __forceinline__ void tp_put(float *sx, int e, float v) {
-    const int j = e / C, c = e - j * C;
-    sx[((j >> 4) * MP3D_TP_PAD + (j & 15)) * C + c] = v;
 }
 
 /* A tile's span into LDS: `span` samples from sample i0 of the call (i0 >=
@@ -139,10 +116,7 @@ k_tp_peak(const float *__restrict__ samples, const TpState *__restrict__ st, con
     __syncthreads();
 
     float tp[MP3D_TP_R - 1][MP3D_TP_TAPS]; /* (phase 0 is the delta) */
-#pragma unroll
-    for (int p = 1; p < MP3D_TP_R; p++)
-#pragma unroll
-        for (int j = 0; j < MP3D_TP_TAPS; j++) tp[p - 1][j] = taps[p * MP3D_TP_TAPS + j];
+    tp_load_taps(taps, tp);
 
     /* this thread's indices: span frames [t SEG, t SEG + cnt + HIST) */
     typedef TpFrame<C> Fr;
@@ -151,20 +125,11 @@ k_tp_peak(const float *__restrict__ samples, const TpState *__restrict__ st, con
     const int lim = cnt ? cnt + MP3D_TP_HIST : 0;
     const T *p = (const T *)sx + t * MP3D_TP_PAD;
     T w[MP3D_TP_SEG + MP3D_TP_HIST];
-#pragma unroll
-    for (int k = 0; k < MP3D_TP_SEG + MP3D_TP_HIST; k++)
-        w[k] = k < lim ? p[(k / MP3D_TP_SEG) * MP3D_TP_PAD + k % MP3D_TP_SEG] : Fr::bc(0.0f);
+    tp_window<C>(p, lim, w);
     float pk = 0.0f;
 #pragma unroll
     for (int i = 0; i < MP3D_TP_SEG; i++) {
-        T a1 = Fr::bc(0.0f), a2 = Fr::bc(0.0f), a3 = Fr::bc(0.0f);
-#pragma unroll
-        for (int j = 0; j < MP3D_TP_TAPS; j++) {
-            a1 = Fr::fma(Fr::bc(tp[0][j]), w[i + j], a1);
-            a2 = Fr::fma(Fr::bc(tp[1][j]), w[i + j], a2);
-            a3 = Fr::fma(Fr::bc(tp[2][j]), w[i + j], a3);
-        }
-        const float v = fmaxf(fmaxf(Fr::amax(w[i + MP3D_TP_PRE]), Fr::amax(a1)), fmaxf(Fr::amax(a2), Fr::amax(a3)));
+        const float v = tp_chain3<C>(w + i, tp); /* (mp3d_tp_chain.h: shared with the limiter's detector) */
         pk = i < cnt ? fmaxf(pk, v) : pk;
     }
 #pragma unroll

@@ -162,6 +162,7 @@ extern "C" int mp3d_batch_set_output(mp3d_batch *b, int out_hz, int out_channels
     b->ld.off(); /* and so does the loudness sink */
     b->nm.off(); /* and the true-peak tap and the gain calls */
     b->sx.off(); /* and the tempo sink */
+    b->lm.off(); /* and the limiter */
     mp3d_batch::PackedSink &k = b->rs;
     if (out_hz == 0) {
         k.off();
@@ -277,6 +278,7 @@ extern "C" int mp3d_batch_set_window(mp3d_batch *b, int first, int n, const long
     if (b->ld.st) HIPCHK(hipMemsetAsync(b->ld.st + first, 0, sizeof(LdState) * (size_t)n, s));
     if (b->nm.st) HIPCHK(hipMemsetAsync(b->nm.st + first, 0, sizeof(TpState) * (size_t)n, s));
     if (b->sx.st) HIPCHK(hipMemsetAsync(b->sx.st + first, 0, sizeof(StState) * (size_t)n, s));
+    if (b->lm.st) HIPCHK(hipMemsetAsync(b->lm.st + first, 0, sizeof(LimState) * (size_t)n, s));
     if (lo)
         HIPCHK(hipMemcpy2DAsync(b->rs.st + first, sizeof(RsState), w.data(), sizeof(RsWindow), sizeof(RsWindow), (size_t)n,
                                 hipMemcpyHostToDevice, s));
