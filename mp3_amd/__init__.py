@@ -249,6 +249,15 @@ def _ptr(x):
     raise TypeError("unsupported buffer type %r" % type(x))
 
 
+def _pack_flags(flush, gapless=False):
+    return (PACK_FLUSH if flush else 0) | (PACK_GAPLESS if gapless else 0)
+
+
+def _stream(stream):
+    """A HIP stream handle (int) as a call's hip_stream argument; None / 0: the handle's own stream."""
+    return ctypes.c_void_p(stream) if stream else None
+
+
 class Decoder:
     """Per-frame decoder (mp3d_decode_frame), one per stream."""
 
@@ -346,6 +355,11 @@ class BatchDecoder:
     def _ck(self, rc):
         return _check(rc, self._L)
 
+    def _stage_us(self, fn):
+        t = ctypes.c_float()
+        self._ck(fn(self._h, ctypes.byref(t)))
+        return float(t.value)
+
     def close(self):
         if getattr(self, "_h", None):
             self._L.mp3d_batch_destroy(self._h)
@@ -393,7 +407,7 @@ class BatchDecoder:
         pp, k2 = _ptr(pcm)
         ip, k3 = _ptr(infos)
         fn = self._L.mp3d_batch_decode_f32 if f32 else self._L.mp3d_batch_decode
-        self._ck(fn(self._h, fp, off.ctypes.data, sz.ctypes.data, n, F, pp, ip, ctypes.c_void_p(stream) if stream else None))
+        self._ck(fn(self._h, fp, off.ctypes.data, sz.ctypes.data, n, F, pp, ip, _stream(stream)))
         return pcm, infos
 
     def set_output(self, hz, channels):
@@ -438,8 +452,7 @@ class BatchDecoder:
         ip, k4 = _ptr(infos)
         self._ck(self._L.mp3d_batch_decode_packed(self._h, fp, off.ctypes.data, sz.ctypes.data, n, F, op, int(bool(f32)),
                                               stride, cp,
-                                              (PACK_FLUSH if flush else 0) | (PACK_GAPLESS if gapless else 0), ip,
-                                              ctypes.c_void_p(stream) if stream else None))
+                                              _pack_flags(flush, gapless), ip, _stream(stream)))
         return out, counts, infos
 
     def set_window(self, lo, hi=None, first=0):
@@ -484,9 +497,7 @@ class BatchDecoder:
     def resample_time_us(self):
         """Device-side microseconds of the resample stage of the last packed
         call (after set_timing)."""
-        t = ctypes.c_float()
-        self._ck(self._L.mp3d_batch_resample_time(self._h, ctypes.byref(t)))
-        return float(t.value)
+        return self._stage_us(self._L.mp3d_batch_resample_time)
 
     def set_features(self, n_mels, log10=True):
         """Turn the log-mel feature sink on (mp3d_batch_set_features): n_mels
@@ -528,8 +539,7 @@ class BatchDecoder:
         cp, k3 = _ptr(counts)
         ip, k4 = _ptr(infos)
         self._ck(self._L.mp3d_batch_decode_features(self._h, fp, off.ctypes.data, sz.ctypes.data, n, F, op, stride, cp,
-                                                    (PACK_FLUSH if flush else 0) | (PACK_GAPLESS if gapless else 0), ip,
-                                                    ctypes.c_void_p(stream) if stream else None))
+                                                    _pack_flags(flush, gapless), ip, _stream(stream)))
         return feat, counts, infos
 
     def features(self, samples, counts, feat=None, feat_counts=None, flush=False, stride=None, stream=None):
@@ -546,15 +556,13 @@ class BatchDecoder:
         op, k3 = _ptr(feat)
         fc, k4 = _ptr(feat_counts)
         self._ck(self._L.mp3d_batch_features(self._h, sp if ss else None, ss, cp, n, op, stride, fc,
-                                             PACK_FLUSH if flush else 0, ctypes.c_void_p(stream) if stream else None))
+                                             _pack_flags(flush), _stream(stream)))
         return feat, feat_counts
 
     def feature_time_us(self):
         """Device-side microseconds of the feature stage of the last feature
         call (after set_timing)."""
-        t = ctypes.c_float()
-        self._ck(self._L.mp3d_batch_feature_time(self._h, ctypes.byref(t)))
-        return float(t.value)
+        return self._stage_us(self._L.mp3d_batch_feature_time)
 
     def set_loudness(self, on=True):
         """Turn the loudness sink on or off (mp3d_batch_set_loudness): ITU-R
@@ -598,7 +606,7 @@ class BatchDecoder:
         bc, k4 = _ptr(block_counts)
         pp, k5 = _ptr(peak)
         self._ck(self._L.mp3d_batch_loudness(self._h, sp if ss else None, ss, cp, n, op, stride, bc, pp,
-                                             PACK_FLUSH if flush else 0, ctypes.c_void_p(stream) if stream else None))
+                                             _pack_flags(flush), _stream(stream)))
         return blocks, block_counts, peak
 
     def decode_loudness(self, frames, offsets, sizes, frames_per_stream, blocks=None, counts=None, peak=None,
@@ -620,8 +628,7 @@ class BatchDecoder:
         pp, k4 = _ptr(peak)
         ip, k5 = _ptr(infos)
         self._ck(self._L.mp3d_batch_decode_loudness(self._h, fp, off.ctypes.data, sz.ctypes.data, n, F, op, stride, cp, pp,
-                                                    (PACK_FLUSH if flush else 0) | (PACK_GAPLESS if gapless else 0), ip,
-                                                    ctypes.c_void_p(stream) if stream else None))
+                                                    _pack_flags(flush, gapless), ip, _stream(stream)))
         return blocks, counts, peak, infos
 
     def integrated_lufs(self, blocks, counts, lufs=None, stream=None):
@@ -638,15 +645,13 @@ class BatchDecoder:
         cp, k2 = _ptr(counts)
         lp, k3 = _ptr(lufs)
         self._ck(self._L.mp3d_batch_loudness_integrated(self._h, bp if stride else None, stride, cp, n, lp,
-                                                        ctypes.c_void_p(stream) if stream else None))
+                                                        _stream(stream)))
         return lufs
 
     def loudness_time_us(self):
         """Device-side microseconds of the loudness stage of the last
         loudness call (after set_timing)."""
-        t = ctypes.c_float()
-        self._ck(self._L.mp3d_batch_loudness_time(self._h, ctypes.byref(t)))
-        return float(t.value)
+        return self._stage_us(self._L.mp3d_batch_loudness_time)
 
     def set_true_peak(self, on=True):
         """Turn the true-peak tap on or off (mp3d_batch_set_true_peak): the
@@ -672,8 +677,8 @@ class BatchDecoder:
         sp, k1 = _ptr(samples)
         cp, k2 = _ptr(counts)
         tp, k3 = _ptr(tpeak)
-        self._ck(self._L.mp3d_batch_true_peak(self._h, sp if ss else None, ss, cp, n, tp, PACK_FLUSH if flush else 0,
-                                              ctypes.c_void_p(stream) if stream else None))
+        self._ck(self._L.mp3d_batch_true_peak(self._h, sp if ss else None, ss, cp, n, tp, _pack_flags(flush),
+                                              _stream(stream)))
         return tpeak
 
     def decode_measure(self, frames, offsets, sizes, frames_per_stream, blocks=None, counts=None, peak=None,
@@ -696,8 +701,7 @@ class BatchDecoder:
         tp, k5 = _ptr(tpeak)
         ip, k6 = _ptr(infos)
         self._ck(self._L.mp3d_batch_decode_measure(self._h, fp, off.ctypes.data, sz.ctypes.data, n, F, op, stride, cp, pp,
-                                                   tp, (PACK_FLUSH if flush else 0) | (PACK_GAPLESS if gapless else 0),
-                                                   ip, ctypes.c_void_p(stream) if stream else None))
+                                                   tp, _pack_flags(flush, gapless), ip, _stream(stream)))
         return blocks, counts, peak, tpeak, infos
 
     def normalize_gain(self, lufs, tpeak=None, target=-23.0, max_dbtp=-1.0, gain=None, stream=None):
@@ -717,7 +721,7 @@ class BatchDecoder:
         tp, k2 = _ptr(tpeak)
         gp, k3 = _ptr(gain)
         self._ck(self._L.mp3d_batch_normalize_gain(self._h, lp, tp, n, float(target), float(max_dbtp), gp,
-                                                   ctypes.c_void_p(stream) if stream else None))
+                                                   _stream(stream)))
         return gain
 
     def apply_gain(self, samples, counts, gain, out=None, f32=True, stream=None):
@@ -739,15 +743,13 @@ class BatchDecoder:
         gp, k3 = _ptr(gain)
         op, k4 = _ptr(out)
         self._ck(self._L.mp3d_batch_apply_gain(self._h, sp if ss else None, ss, cp, n, gp, op, int(bool(f32)),
-                                               ctypes.c_void_p(stream) if stream else None))
+                                               _stream(stream)))
         return out
 
     def true_peak_time_us(self):
         """Device-side microseconds of the true-peak stage of the last
         true-peak call (after set_timing)."""
-        t = ctypes.c_float()
-        self._ck(self._L.mp3d_batch_true_peak_time(self._h, ctypes.byref(t)))
-        return float(t.value)
+        return self._stage_us(self._L.mp3d_batch_true_peak_time)
 
     def set_stretch(self, on=True):
         """Turn the tempo sink on or off (mp3d_batch_set_stretch): a
@@ -799,7 +801,7 @@ class BatchDecoder:
         op, k3 = _ptr(out)
         oc, k4 = _ptr(out_counts)
         self._ck(self._L.mp3d_batch_stretch(self._h, sp if ss else None, ss, cp, n, op, stride, oc,
-                                            PACK_FLUSH if flush else 0, ctypes.c_void_p(stream) if stream else None))
+                                            _pack_flags(flush), _stream(stream)))
         return out, out_counts
 
     def decode_stretched(self, frames, offsets, sizes, frames_per_stream, out=None, counts=None, infos=None,
@@ -820,16 +822,13 @@ class BatchDecoder:
         cp, k3 = _ptr(counts)
         ip, k4 = _ptr(infos)
         self._ck(self._L.mp3d_batch_decode_stretched(self._h, fp, off.ctypes.data, sz.ctypes.data, n, F, op, stride, cp,
-                                                     (PACK_FLUSH if flush else 0) | (PACK_GAPLESS if gapless else 0),
-                                                     ip, ctypes.c_void_p(stream) if stream else None))
+                                                     _pack_flags(flush, gapless), ip, _stream(stream)))
         return out, counts, infos
 
     def stretch_time_us(self):
         """Device-side microseconds of the stretch stage of the last stretch
         call (after set_timing)."""
-        t = ctypes.c_float()
-        self._ck(self._L.mp3d_batch_stretch_time(self._h, ctypes.byref(t)))
-        return float(t.value)
+        return self._stage_us(self._L.mp3d_batch_stretch_time)
 
     def set_limiter(self, on=True, ceiling_db=-1.0):
         """Turn the look-ahead true-peak limiter on or off
@@ -882,7 +881,7 @@ class BatchDecoder:
         oc, k5 = _ptr(out_counts)
         rp, k6 = _ptr(gr)
         self._ck(self._L.mp3d_batch_limit(self._h, sp if ss else None, ss, cp, n, gp, op, int(bool(f32)), stride, oc, rp,
-                                          PACK_FLUSH if flush else 0, ctypes.c_void_p(stream) if stream else None))
+                                          _pack_flags(flush), _stream(stream)))
         return out, out_counts, gr
 
     def decode_limited(self, frames, offsets, sizes, frames_per_stream, gain=None, out=None, counts=None, gr=None,
@@ -906,16 +905,13 @@ class BatchDecoder:
         ip, k6 = _ptr(infos)
         self._ck(self._L.mp3d_batch_decode_limited(self._h, fp, off.ctypes.data, sz.ctypes.data, n, F, gp, op,
                                                    int(bool(f32)), stride, cp, rp,
-                                                   (PACK_FLUSH if flush else 0) | (PACK_GAPLESS if gapless else 0), ip,
-                                                   ctypes.c_void_p(stream) if stream else None))
+                                                   _pack_flags(flush, gapless), ip, _stream(stream)))
         return out, counts, gr, infos
 
     def limiter_time_us(self):
         """Device-side microseconds of the limiter stage of the last limiter
         call (after set_timing)."""
-        t = ctypes.c_float()
-        self._ck(self._L.mp3d_batch_limiter_time(self._h, ctypes.byref(t)))
-        return float(t.value)
+        return self._stage_us(self._L.mp3d_batch_limiter_time)
 
     def decode_normalized(self, frames, offsets, sizes, frames_per_stream, target=-23.0, max_dbtp=-1.0, out=None,
                           f32=True, gapless=False, limit=False):
@@ -1094,8 +1090,7 @@ class BatchDecoder:
         bp, k2 = _ptr(block_type)
         mp, k3 = _ptr(mixed)
         pp, k4 = _ptr(pcm)
-        self._ck(self._L.mp3d_batch_synth_only(self._h, xp, bp, mp, n, F, int(nch), int(hz), pp,
-                                           ctypes.c_void_p(stream) if stream else None))
+        self._ck(self._L.mp3d_batch_synth_only(self._h, xp, bp, mp, n, F, int(nch), int(hz), pp, _stream(stream)))
         return pcm
 
 

@@ -196,11 +196,7 @@ extern "C" int mp3d_batch_reset(mp3d_batch *b) {
     b->tail_live = -1; /* the state is zeroed whole */
     HIPCHK(state_clear(b->st, b->max_streams, b->own));
     if (b->rs.st) HIPCHK(hipMemsetAsync(b->rs.st, 0, sizeof(RsState) * (size_t)b->max_streams, b->own));
-    if (b->ft.st) HIPCHK(hipMemsetAsync(b->ft.st, 0, sizeof(FtState) * (size_t)b->max_streams, b->own));
-    if (b->ld.st) HIPCHK(hipMemsetAsync(b->ld.st, 0, sizeof(LdState) * (size_t)b->max_streams, b->own));
-    if (b->nm.st) HIPCHK(hipMemsetAsync(b->nm.st, 0, sizeof(TpState) * (size_t)b->max_streams, b->own));
-    if (b->sx.st) HIPCHK(hipMemsetAsync(b->sx.st, 0, sizeof(StState) * (size_t)b->max_streams, b->own));
-    if (b->lm.st) HIPCHK(hipMemsetAsync(b->lm.st, 0, sizeof(LimState) * (size_t)b->max_streams, b->own));
+    RCCHK(stages_restart(b, 0, b->max_streams, b->own));
     HIPCHK(hipStreamSynchronize(b->own));
     return MP3D_OK;
 }
@@ -654,11 +650,7 @@ static int state_copy(mp3d_batch *b, int first, int n, void *dst, const void *sr
                           hipMemcpyDefault, s));
     /* a restored state is a discontinuity: the slots' resamplers restart */
     if (!out && b->rs.st) HIPCHK(hipMemsetAsync(b->rs.st + first, 0, sizeof(RsState) * (size_t)n, s));
-    if (!out && b->ft.st) HIPCHK(hipMemsetAsync(b->ft.st + first, 0, sizeof(FtState) * (size_t)n, s));
-    if (!out && b->ld.st) HIPCHK(hipMemsetAsync(b->ld.st + first, 0, sizeof(LdState) * (size_t)n, s));
-    if (!out && b->nm.st) HIPCHK(hipMemsetAsync(b->nm.st + first, 0, sizeof(TpState) * (size_t)n, s));
-    if (!out && b->sx.st) HIPCHK(hipMemsetAsync(b->sx.st + first, 0, sizeof(StState) * (size_t)n, s));
-    if (!out && b->lm.st) HIPCHK(hipMemsetAsync(b->lm.st + first, 0, sizeof(LimState) * (size_t)n, s));
+    if (!out) RCCHK(stages_restart(b, first, n, s));
     HIPCHK(hipStreamSynchronize(s));
     return MP3D_OK;
 }

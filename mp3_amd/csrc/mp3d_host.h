@@ -1,8 +1,9 @@
 /*
  * mp3d_host.h -- private to the host sources (mp3d_host_tables.cpp,
  * mp3d_batch.cpp, mp3d_long.cpp, mp3d_dec.cpp, mp3d_sinks.cpp,
- * mp3d_loudness.cpp, mp3d_normalize.cpp, mp3d_stretch.cpp, mp3d_limiter.cpp): the error
- * macro, the owning device buffer, the batch handle and the internal
+ * mp3d_loudness.cpp, mp3d_normalize.cpp, mp3d_stretch.cpp, mp3d_limiter.cpp):
+ * the error macros, the owning device buffer, the batch handle, the frame
+ * that the calls of the stages behind the packed sink share, and the internal
  * functions that cross those files.  Nothing here is exported (the library
  * is built with hidden visibility; the C ABI is include/mp3d.h).
  */
@@ -40,10 +41,12 @@ inline int hip_rc(hipError_t e) {
     g_last_hip = (int)e;
     return e == hipErrorOutOfMemory ? MP3D_E_NOMEM : MP3D_E_HIP;
 }
-#define HIPCHK(x)                                                                                                      \
+/* return an MP3D_* failure (RCCHK) or a HIP one (HIPCHK) to the caller */
+#define RCCHK(x)                                                                                                       \
     do {                                                                                                               \
-        if (const int _rc = mp3d::hip_rc(x)) return _rc;                                                               \
+        if (const int _rc = (x)) return _rc;                                                                           \
     } while (0)
+#define HIPCHK(x) RCCHK(mp3d::hip_rc(x))
 
 /* per-device one-time init: constant symbols + table buffer (mp3d_host_tables.cpp) */
 struct DeviceCtx {
@@ -211,119 +214,105 @@ struct mp3d_batch {
     /* mp3d_batch_decode_long_packed to a rate other than the sink's: the
      * filters of its last output rate, kept for the next call */
     mp3d::RsFilters lp;
+    /* What every stage downstream of the packed sink has (DESIGN.md section
+     * 4d): a call's inputs when they are not the caller's own device memory
+     * (smp: a host caller's samples or the packed samples of the stage's
+     * decode_* call; cin: their counts), staging for a host caller's outputs
+     * (out: rows; cnt: their counts) and the stage's timer.  cin and cnt hold
+     * max_streams entries; smp and out grow with the calls.  A stage leaves
+     * what it does not use empty. */
+    struct Stage {
+        mp3d::DevBuf<float> smp;
+        mp3d::DevBuf<int32_t> cin, cnt;
+        mp3d::DevBuf<void> out;
+        mp3d::StageTimer tm;
+        void off() {
+            smp.release(), cin.release(), cnt.release(), out.release();
+            tm.timed = false;
+        }
+    };
     /* log-mel feature sink (mp3d_batch_set_features; mp3d_features.h):
-     * mels = 0 is off, and then none of these buffers exists.  st, plan, cin
-     * (sample counts of a call) and cnt hold max_streams entries; smp (the
-     * samples of a call) and out (staging for a host sink) grow with the
-     * calls. */
-    struct FeatureSink {
+     * mels = 0 is off, and then none of its buffers exists.  st and plan hold
+     * max_streams entries. */
+    struct FeatureSink : Stage {
         int mels = 0;
         mp3d::DevBuf<FtTab> tab;
         mp3d::DevBuf<FtState> st;
         mp3d::DevBuf<FtPlan> plan;
-        mp3d::DevBuf<int32_t> cin, cnt;
-        mp3d::DevBuf<float> smp, out;
-        mp3d::StageTimer tm;
         void off() {
-            tab.release(), st.release(), plan.release(), cin.release(), cnt.release(), smp.release(), out.release();
+            Stage::off(), tab.release(), st.release(), plan.release();
             mels = 0;
-            tm.timed = false;
         }
     } ft;
     /* loudness sink (mp3d_batch_set_loudness; mp3d_loudness.h): on = false is
-     * off, and then none of these buffers exists.  st, plan, cin, cnt, pk, lu
-     * (integrated loudness of a call's rows) and endst hold max_streams
-     * entries; smp, out (staging for a host sink) and the per-tile scratch
-     * tz, entry, part, tpeak grow with the calls. */
-    struct LoudnessSink {
+     * off, and then none of its buffers exists.  st, plan, pk, lu (integrated
+     * loudness of a call's rows) and endst hold max_streams entries; the
+     * per-tile scratch tz, entry, part, tpeak grows with the calls. */
+    struct LoudnessSink : Stage {
         bool on = false;
         int H = 0;
         mp3d::DevBuf<LdTab> tab;
         mp3d::DevBuf<LdState> st;
         mp3d::DevBuf<LdPlan> plan;
-        mp3d::DevBuf<int32_t> cin, cnt;
-        mp3d::DevBuf<float> smp, out, pk, lu, tpeak;
+        mp3d::DevBuf<float> pk, lu, tpeak;
         mp3d::DevBuf<double> tz, entry, part, endst;
-        mp3d::StageTimer tm;
         void off() {
-            tab.release(), st.release(), plan.release(), cin.release(), cnt.release(), smp.release(), out.release();
-            pk.release(), lu.release(), tpeak.release(), tz.release(), entry.release(), part.release(), endst.release();
+            Stage::off(), tab.release(), st.release(), plan.release(), pk.release(), lu.release(), tpeak.release();
+            tz.release(), entry.release(), part.release(), endst.release();
             on = false, H = 0;
-            tm.timed = false;
         }
     } ld;
-    /* true-peak tap and gain (mp3d_batch_set_true_peak; mp3d_normalize.h):
-     * on = false is off, and then taps, st and plan do not exist.  st, plan,
-     * cin, tp hold max_streams entries; smp (a host caller's samples) and the
-     * per-tile scratch tile grow with the calls.  The gain calls need only a
-     * packed format: their staging (lu, gtp, gain for host arrays of the gain
-     * rule; ccnt, gsmp, gcin, gg, out of mp3d_batch_apply_gain) is made by the
-     * first call that needs it and freed with the packed format. */
-    struct NormalizeSink {
+    /* true-peak tap (mp3d_batch_set_true_peak; mp3d_normalize.h): on = false
+     * is off, and then none of its buffers exists.  st, plan and tp hold
+     * max_streams entries; the per-tile scratch tile grows with the calls. */
+    struct TruePeakTap : Stage {
         bool on = false;
-        mp3d::DevBuf<float> taps;
+        mp3d::DevBuf<float> taps, tile, tp;
         mp3d::DevBuf<TpState> st;
         mp3d::DevBuf<TpPlan> plan;
-        mp3d::DevBuf<int32_t> cin, ccnt, gcin;
-        mp3d::DevBuf<float> smp, tile, tp, lu, gtp, gain, gsmp, gg;
-        mp3d::DevBuf<void> out;
-        mp3d::StageTimer tm;
-        /* the tap: the gain calls' staging stays */
-        void tap_off() {
-            taps.release(), st.release(), plan.release(), cin.release(), smp.release(), tile.release(), tp.release();
-            on = false;
-            tm.timed = false;
-        }
         void off() {
-            tap_off();
-            ccnt.release(), gcin.release(), lu.release(), gtp.release(), gain.release(), gsmp.release(), gg.release();
-            out.release();
+            Stage::off(), taps.release(), tile.release(), tp.release(), st.release(), plan.release();
+            on = false;
         }
     } nm;
+    /* The gain calls (mp3d_batch_normalize_gain, mp3d_batch_apply_gain) need
+     * only a packed format: their staging (lu, gtp, gain for host arrays of
+     * the gain rule; smp, cin, gg, out and the clamped counts cnt of
+     * mp3d_batch_apply_gain) is made by the first call that needs it and
+     * freed with the packed format. */
+    struct GainCalls : Stage {
+        mp3d::DevBuf<float> lu, gtp, gain, gg;
+        void off() { Stage::off(), lu.release(), gtp.release(), gain.release(), gg.release(); }
+    } ga;
     /* tempo sink (mp3d_batch_set_stretch; mp3d_stretch.h): on = false is off,
-     * and then none of these buffers exists.  st, plan, tempo (num, den per
-     * slot; it outlives a restart of st), cin and cnt hold max_streams
-     * entries; smp (a host caller's samples, or the packed samples of
-     * mp3d_batch_decode_stretched) and out (staging for a host sink) grow with
-     * the calls. */
-    struct StretchSink {
+     * and then none of its buffers exists.  st, plan and tempo (num, den per
+     * slot; it outlives a restart of st) hold max_streams entries. */
+    struct StretchSink : Stage {
         bool on = false;
         int H = 0;
         mp3d::DevBuf<float> w;
         mp3d::DevBuf<StState> st;
         mp3d::DevBuf<StPlan> plan;
-        mp3d::DevBuf<int32_t> tempo, cin, cnt;
-        mp3d::DevBuf<float> smp, out;
-        mp3d::StageTimer tm;
+        mp3d::DevBuf<int32_t> tempo;
         void off() {
-            w.release(), st.release(), plan.release(), tempo.release(), cin.release(), cnt.release(), smp.release();
-            out.release();
+            Stage::off(), w.release(), st.release(), plan.release(), tempo.release();
             on = false, H = 0;
-            tm.timed = false;
         }
     } sx;
     /* limiter (mp3d_batch_set_limiter; mp3d_limiter.h): on = false is off, and
-     * then none of these buffers exists.  taps, st, plan, cin, cnt, gg (a host
-     * caller's gains) and grd (gr for a host caller) hold max_streams entries;
-     * smp (a host caller's samples, or the packed samples of
-     * mp3d_batch_decode_limited), out (staging for a host sink) and the
-     * per-tile scratch tile grow with the calls. */
-    struct LimiterSink {
+     * then none of its buffers exists.  taps, st, plan, gg (a host caller's
+     * gains) and grd (gr for a host caller) hold max_streams entries; the
+     * per-tile scratch tile grows with the calls. */
+    struct LimiterSink : Stage {
         bool on = false;
         int A = 0;
         float c = 1.0f; /* the ceiling, linear */
-        mp3d::DevBuf<float> taps;
+        mp3d::DevBuf<float> taps, gg, grd, tile;
         mp3d::DevBuf<LimState> st;
         mp3d::DevBuf<LimPlan> plan;
-        mp3d::DevBuf<int32_t> cin, cnt;
-        mp3d::DevBuf<float> smp, gg, grd, tile;
-        mp3d::DevBuf<void> out;
-        mp3d::StageTimer tm;
         void off() {
-            taps.release(), st.release(), plan.release(), cin.release(), cnt.release(), smp.release(), gg.release();
-            grd.release(), tile.release(), out.release();
+            Stage::off(), taps.release(), gg.release(), grd.release(), tile.release(), st.release(), plan.release();
             on = false, A = 0, c = 1.0f;
-            tm.timed = false;
         }
     } lm;
 };
@@ -371,15 +360,108 @@ struct CallEnd {
     }
 };
 
-/* ---- mp3d_batch.cpp ---- */
 /* Where a caller's buffer lives, seen from the handle's device: its own
  * device memory (or managed memory) is read and written in place by the
  * kernels; host memory and another GPU's memory are staged through the
- * handle's buffers with hipMemcpyDefault copies (no peer access assumed). */
+ * handle's buffers with hipMemcpyDefault copies (no peer access assumed).
+ * (mp3d_batch.cpp) */
 enum PtrKind { PTR_HOST, PTR_DEV, PTR_OTHER_DEV };
 PtrKind ptr_kind(const void *p, int device);
 /* memory the handle's kernels may read / write in place */
 inline bool is_device_ptr(const void *p, int device) { return ptr_kind(p, device) == PTR_DEV; }
+
+/* The stages downstream of the packed sink, listed once. A new sink adds its
+ * line to stages_off and to stages_restart, and its timer to the two loops
+ * over the timers in mp3d_batch.cpp (create, destroy); nothing else names
+ * them all. */
+/* they read the packed sink's format: off with any change of it */
+inline void stages_off(mp3d_batch *b) { b->ft.off(), b->ld.off(), b->nm.off(), b->ga.off(), b->sx.off(), b->lm.off(); }
+template <class S> hipError_t stage_restart(const DevBuf<S> &st, int first, int n, hipStream_t s) {
+    return st ? hipMemsetAsync(st + first, 0, sizeof(S) * (size_t)n, s) : hipSuccess;
+}
+/* slots [first, first + n) of every stage that is on start a new stream, on stream s */
+inline int stages_restart(mp3d_batch *b, int first, int n, hipStream_t s) {
+    HIPCHK(stage_restart(b->ft.st, first, n, s));
+    HIPCHK(stage_restart(b->ld.st, first, n, s));
+    HIPCHK(stage_restart(b->nm.st, first, n, s));
+    HIPCHK(stage_restart(b->sx.st, first, n, s));
+    HIPCHK(stage_restart(b->lm.st, first, n, s));
+    return MP3D_OK;
+}
+
+/* ---- the frame of a stage's calls ---- */
+/* the head of a set_* call: the handle idle, its last call done */
+inline int set_begin(mp3d_batch *b) {
+    HIPCHK(hipSetDevice(b->device));
+    RCCHK(own_after_last(b));
+    HIPCHK(hipStreamSynchronize(b->own));
+    return MP3D_OK;
+}
+/* its tail, r the result so far: the uploads waited for (they read the
+ * caller's stack), and after a failure stage k is off */
+template <class K> int set_end(mp3d_batch *b, K &k, int r) {
+    if (!r) r = hip_rc(hipStreamSynchronize(b->own));
+    if (r) k.off();
+    k.tm.timed = false;
+    return r;
+}
+
+/* One launch of a stage on stream s: between the timer's events when the
+ * handle times its stages (tm = null: an untimed small kernel), after the
+ * LDS poison when the handle poisons */
+template <class F> int stage_launch(mp3d_batch *b, StageTimer *tm, hipStream_t s, F &&launch) {
+    if (!b->timing) tm = nullptr;
+    if (tm) HIPCHK(tm->begin(s));
+    if (b->poison) launch_lds_poison(g_dev[b->device].n_cu, s);
+    launch();
+    if (tm) HIPCHK(tm->end(s));
+    return hip_rc(hipGetLastError());
+}
+
+/* behind the *_time exports */
+inline int stage_time(const mp3d_batch *b, const StageTimer &tm, float *us) {
+    if (!us || !b->timing || !tm.timed) return MP3D_E_ARG;
+    return tm.elapsed_us(us);
+}
+
+/* A caller's n-element array (or null) for a kernel to read on stream s:
+ * itself when it is device memory (element-aligned, else MP3D_E_ARG), else a
+ * copy in `stage` (max_streams elements); *host is set when the caller's host
+ * memory is read, until the stream reaches the copy's end */
+template <class T>
+int caller_in(mp3d_batch *b, const T *p, int n, DevBuf<T> &stage, hipStream_t s, const T **dev, bool *host) {
+    *dev = p;
+    if (!p) return MP3D_OK;
+    if (is_device_ptr(p, b->device)) return (uintptr_t)p % sizeof(T) ? MP3D_E_ARG : MP3D_OK;
+    RCCHK(stage.grow(b, sizeof(T) * (size_t)b->max_streams));
+    HIPCHK(hipMemcpyAsync(stage.p, p, sizeof(T) * (size_t)n, hipMemcpyDefault, s));
+    *dev = stage.p;
+    *host = true;
+    return MP3D_OK;
+}
+
+/* A caller's n-element array (or null) for a kernel to write: dev is the
+ * array itself when it is device memory (element-aligned, else MP3D_E_ARG),
+ * else `stage` (max_streams elements), and then copy_back queues the copy to
+ * the caller after the kernel; the caller of copy_back waits. */
+template <class T> struct CallerOut {
+    T *user = nullptr, *dev = nullptr;
+    bool host = false; /* dev is the staging */
+    int pick(mp3d_batch *b, T *p, DevBuf<T> &stage) {
+        user = dev = p;
+        if (!p) return MP3D_OK;
+        if (is_device_ptr(p, b->device)) return (uintptr_t)p % sizeof(T) ? MP3D_E_ARG : MP3D_OK;
+        RCCHK(stage.grow(b, sizeof(T) * (size_t)b->max_streams));
+        dev = stage.p;
+        host = true;
+        return MP3D_OK;
+    }
+    hipError_t copy_back(int n, hipStream_t s) const {
+        return host ? hipMemcpyAsync(user, dev, sizeof(T) * (size_t)n, hipMemcpyDefault, s) : hipSuccess;
+    }
+};
+
+/* ---- mp3d_batch.cpp ---- */
 /* StreamState slots [0, n) zeroed with their format stamp, on stream s (the
  * caller orders / waits) */
 hipError_t state_clear(StreamState *st, int n, hipStream_t s);
@@ -430,6 +512,21 @@ long long rs_bound(int in_hz, int out_hz, long long frames);
  * it is done. */
 int deliver_rows(hipStream_t s, int n, size_t unit, const void *drows, long long dstride, void *rows, long long stride,
                  const int32_t *dcnt, int *count, bool rows_dev, bool cnt_dev);
+/* The inputs of a stage's call on the caller's samples [n][stride] (`frame`
+ * bytes per sample frame) and counts [n], for the kernels on stream s: each
+ * is the caller's own when it is device memory (float- / int-aligned, else
+ * MP3D_E_ARG), else a copy in k.smp / k.cin.  *host as in caller_in. */
+int stage_inputs(mp3d_batch *b, mp3d_batch::Stage &k, const float *samples, long long stride, size_t frame,
+                 const int *counts, int n, hipStream_t s, const float **dsmp, const int32_t **dcin, bool *host);
+/* the stride of a decode_* call's packed samples: one no stream of F frames can exceed */
+inline long long stage_stride(const mp3d_batch *b, int F) { return mp3d_packed_max_samples(b->rs.f.hz, F, 0); }
+/* The head of a stage's decode_* call, after the wrapper's own checks: the
+ * checks they share (argument errors before capacity errors), then the packed
+ * call into the stage's own samples k.smp [n][*S] and counts k.cin, which only
+ * queues work; *s is the call's stream. */
+int decode_to_stage(mp3d_batch *b, mp3d_batch::Stage &k, const uint8_t *frames, const uint64_t *offsets,
+                    const uint32_t *sizes, int n, int F, int flags, mp3d_frame_info *infos, void *hip_stream,
+                    long long *S, hipStream_t *s);
 
 } // namespace mp3d
 

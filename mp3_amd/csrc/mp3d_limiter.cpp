@@ -28,10 +28,7 @@ extern "C" long long mp3d_limiter_max_samples(int hz, long long in_samples) {
 
 extern "C" int mp3d_batch_set_limiter(mp3d_batch *b, int on, double ceiling_db) {
     if (!b || (on && (!b->rs.f.hz || !(ceiling_db >= -20.0 && ceiling_db <= 0.0)))) return MP3D_E_ARG;
-    HIPCHK(hipSetDevice(b->device));
-    int r = own_after_last(b);
-    if (r) return r;
-    HIPCHK(hipStreamSynchronize(b->own));
+    RCCHK(set_begin(b));
     mp3d_batch::LimiterSink &k = b->lm;
     if (!on) {
         k.off();
@@ -41,7 +38,7 @@ extern "C" int mp3d_batch_set_limiter(mp3d_batch *b, int on, double ceiling_db) 
     float taps[MP3D_TP_R * MP3D_TP_TAPS];
     (void)mp3d_truepeak_filter(taps, MP3D_TP_R * MP3D_TP_TAPS);
     const size_t ns = (size_t)b->max_streams;
-    r = k.taps.grow(b, sizeof(taps));
+    int r = k.taps.grow(b, sizeof(taps));
     if (!r) r = k.st.grow(b, sizeof(LimState) * ns);
     if (!r) r = k.plan.grow(b, sizeof(LimPlan) * ns);
     if (!r) r = k.cin.grow(b, sizeof(int32_t) * ns);
@@ -51,12 +48,10 @@ extern "C" int mp3d_batch_set_limiter(mp3d_batch *b, int on, double ceiling_db) 
     if (!r) r = hip_rc(hipMemcpyAsync(k.taps, taps, sizeof(taps), hipMemcpyHostToDevice, b->own));
     /* setting the limiter restarts every stream's limiter state */
     if (!r) r = hip_rc(hipMemsetAsync(k.st, 0, sizeof(LimState) * ns, b->own));
-    if (!r) r = hip_rc(hipStreamSynchronize(b->own)); /* (taps is read until here) */
-    if (r) k.off();
+    r = set_end(b, k, r); /* (taps is read until here) */
     k.on = !r;
     k.A = r ? 0 : lim_ahead(b->rs.f.hz);
     k.c = r ? 1.0f : (float)pow(10.0, ceiling_db / 20.0);
-    k.tm.timed = false;
     return r;
 }
 
@@ -69,44 +64,28 @@ static int lim_run(mp3d_batch *b, const float *dsmp, const int32_t *dcin, long l
     mp3d_batch::LimiterSink &k = b->lm;
     const int oc = b->rs.ch;
     const size_t eb = f32 ? sizeof(float) : sizeof(int16_t);
-    const bool out_dev = is_device_ptr(out, b->device), cnt_dev = is_device_ptr(out_count, b->device);
-    const bool gr_dev = gr && is_device_ptr(gr, b->device);
+    const bool out_dev = is_device_ptr(out, b->device);
     /* (the alignment rule of mp3d_batch_apply_gain's out) */
     if (out_dev && (uintptr_t)out % (eb * oc)) return MP3D_E_ARG;
-    if (cnt_dev && (uintptr_t)out_count % sizeof(int32_t)) return MP3D_E_ARG;
-    if (gr_dev && (uintptr_t)gr % sizeof(float)) return MP3D_E_ARG;
+    CallerOut<int32_t> cnt;
+    CallerOut<float> gro;
+    RCCHK(cnt.pick(b, (int32_t *)out_count, k.cnt));
+    RCCHK(gro.pick(b, gr, k.grd));
     /* no call emits more than its samples plus the A + 6 it found pending */
     const long long most = sstride + MP3D_LIM_AHEAD(k.A), stride = std::min(out_stride, most);
     const long long tiles = std::max<long long>(1, (std::min(most, out_stride) + MP3D_LIM_TILE - 1) / MP3D_LIM_TILE);
     /* one block per (stream, tile): the grid's blocks fit int and its threads 32 bits */
     if (tiles * n > 0x7fffffffLL || tiles * n * MP3D_LIM_THREADS > 0xffffffffLL) return MP3D_E_CAPACITY;
-    int r = k.tile.grow(b, sizeof(float) * (size_t)n * (size_t)tiles);
-    if (!r && !out_dev) r = k.out.grow(b, eb * oc * (size_t)stride * n + 16);
-    if (r) return r;
+    RCCHK(k.tile.grow(b, sizeof(float) * (size_t)n * (size_t)tiles));
+    if (!out_dev) RCCHK(k.out.grow(b, eb * oc * (size_t)stride * n + 16));
     void *dout = out_dev ? out : k.out.p;
-    int32_t *dcnt = cnt_dev ? (int32_t *)out_count : k.cnt.p;
-    float *dgr = !gr ? nullptr : gr_dev ? gr : k.grd.p;
-    if (b->timing) HIPCHK(k.tm.begin(s));
-    if (b->poison) launch_lds_poison(g_dev[b->device].n_cu, s);
-    launch_limiter(dsmp, dcin, k.st, k.plan, k.taps, dgain, dout, dcnt, k.tile, dgr, f32 != 0, oc, n, sstride,
-                   out_dev ? out_stride : stride, (int)tiles, k.A, k.c, (flags & MP3D_PACK_FLUSH) ? 1 : 0, s);
-    if (b->timing) HIPCHK(k.tm.end(s));
-    HIPCHK(hipGetLastError());
-    if (gr && !gr_dev) HIPCHK(hipMemcpyAsync(gr, dgr, sizeof(float) * n, hipMemcpyDefault, s));
-    r = deliver_rows(s, n, eb * oc, dout, stride, out, out_stride, dcnt, out_count, out_dev, cnt_dev);
-    if (r) return r;
-    if (gr && !gr_dev) HIPCHK(hipStreamSynchronize(s));
-    return MP3D_OK;
-}
-
-/* a caller's gains for the kernels: themselves when device memory, else a copy */
-static int lim_gain(mp3d_batch *b, const float *gain, int n, hipStream_t s, const float **dev, bool *host) {
-    *dev = gain;
-    if (!gain) return MP3D_OK;
-    if (is_device_ptr(gain, b->device)) return (uintptr_t)gain % sizeof(float) ? MP3D_E_ARG : MP3D_OK;
-    HIPCHK(hipMemcpyAsync(b->lm.gg, gain, sizeof(float) * (size_t)n, hipMemcpyDefault, s));
-    *dev = b->lm.gg;
-    *host = true;
+    RCCHK(stage_launch(b, &k.tm, s, [&] {
+        launch_limiter(dsmp, dcin, k.st, k.plan, k.taps, dgain, dout, cnt.dev, k.tile, gro.dev, f32 != 0, oc, n, sstride,
+                       out_dev ? out_stride : stride, (int)tiles, k.A, k.c, (flags & MP3D_PACK_FLUSH) ? 1 : 0, s);
+    }));
+    HIPCHK(gro.copy_back(n, s));
+    RCCHK(deliver_rows(s, n, eb * oc, dout, stride, out, out_stride, cnt.dev, out_count, out_dev, !cnt.host));
+    if (gro.host) HIPCHK(hipStreamSynchronize(s));
     return MP3D_OK;
 }
 
@@ -119,39 +98,21 @@ extern "C" int mp3d_batch_limit(mp3d_batch *b, const float *samples, long long s
     if ((!samples && sample_stride) || n <= 0) return MP3D_E_ARG;
     if (n > b->max_streams) return MP3D_E_CAPACITY;
     if (sample_stride > LIM_MAX_STRIDE || out_stride > LIM_MAX_STRIDE) return MP3D_E_ARG;
-    const size_t row = sizeof(float) * (size_t)sample_stride * b->rs.ch;
+    const size_t frame = sizeof(float) * b->rs.ch, row = frame * (size_t)sample_stride;
     const size_t orow = (f32 ? sizeof(float) : sizeof(int16_t)) * (size_t)out_stride * b->rs.ch;
     /* a tile reads its halo after its neighbours wrote their outputs: not in place */
     const uintptr_t s0 = (uintptr_t)samples, o0 = (uintptr_t)out;
     if (row && orow && s0 < o0 + orow * n && o0 < s0 + row * n) return MP3D_E_ARG;
     HIPCHK(hipSetDevice(b->device));
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : b->own;
-    int r = call_begin(b, s);
-    if (r) return r;
+    RCCHK(call_begin(b, s));
     CallEnd done{b, s};
-    const float *dsmp = samples, *dg = nullptr;
-    const int32_t *dcin = (const int32_t *)counts;
+    const float *dsmp, *dg;
+    const int32_t *dcin;
     bool host_in = false;
-    if (sample_stride && !is_device_ptr(samples, b->device)) {
-        r = b->lm.smp.grow(b, row * n);
-        if (r) return r;
-        HIPCHK(hipMemcpyAsync(b->lm.smp, samples, row * n, hipMemcpyDefault, s));
-        dsmp = b->lm.smp;
-        host_in = true;
-    } else if (sample_stride && (uintptr_t)samples % sizeof(float)) {
-        return MP3D_E_ARG;
-    }
-    if (!is_device_ptr(counts, b->device)) {
-        HIPCHK(hipMemcpyAsync(b->lm.cin, counts, sizeof(int32_t) * n, hipMemcpyDefault, s));
-        dcin = b->lm.cin;
-        host_in = true;
-    } else if ((uintptr_t)counts % sizeof(int32_t)) {
-        return MP3D_E_ARG;
-    }
-    r = lim_gain(b, gain, n, s, &dg, &host_in);
-    if (r) return r;
-    r = lim_run(b, dsmp, dcin, sample_stride, n, dg, out, f32, out_stride, out_count, gr, flags, s);
-    if (r) return r;
+    RCCHK(stage_inputs(b, b->lm, samples, sample_stride, frame, counts, n, s, &dsmp, &dcin, &host_in));
+    RCCHK(caller_in(b, gain, n, b->lm.gg, s, &dg, &host_in));
+    RCCHK(lim_run(b, dsmp, dcin, sample_stride, n, dg, out, f32, out_stride, out_count, gr, flags, s));
     if (host_in) HIPCHK(hipStreamSynchronize(s)); /* the caller's host arrays are read until here */
     return MP3D_OK;
 }
@@ -160,31 +121,19 @@ extern "C" int mp3d_batch_decode_limited(mp3d_batch *b, const uint8_t *frames, c
                                          const uint32_t *sizes, int n, int F, const float *gain, void *out, int f32,
                                          long long out_stride, int *out_count, float *gr, int flags,
                                          mp3d_frame_info *infos, void *hip_stream) {
-    if (!b || !b->lm.on || !out || !out_count || out_stride < 0 || out_stride > LIM_MAX_STRIDE ||
-        (flags & ~(MP3D_PACK_FLUSH | MP3D_PACK_GAPLESS)))
-        return MP3D_E_ARG;
-    if (!frames || !offsets || !sizes || n <= 0 || F <= 0) return MP3D_E_ARG;
-    if (n > b->max_streams || F > b->max_frames) return MP3D_E_CAPACITY;
-    HIPCHK(hipSetDevice(b->device));
-    /* the packed call into the handle's own samples: a stride no stream can
-     * exceed, counts on the device, so it only queues work */
-    const long long S = mp3d_packed_max_samples(b->rs.f.hz, F, 0);
-    int r = b->lm.smp.grow(b, sizeof(float) * (size_t)S * b->rs.ch * n);
-    if (r) return r;
-    r = mp3d_batch_decode_packed(b, frames, offsets, sizes, n, F, b->lm.smp, 1, S, b->lm.cin, flags, infos, hip_stream);
-    if (r) return r;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : b->own;
+    if (!b || !b->lm.on || !out || !out_count || out_stride < 0 || out_stride > LIM_MAX_STRIDE) return MP3D_E_ARG;
+    long long S;
+    hipStream_t s;
+    RCCHK(decode_to_stage(b, b->lm, frames, offsets, sizes, n, F, flags, infos, hip_stream, &S, &s));
     CallEnd done{b, s};
-    const float *dg = nullptr;
+    const float *dg;
     bool host_in = false;
-    r = lim_gain(b, gain, n, s, &dg, &host_in);
-    if (!r) r = lim_run(b, b->lm.smp, b->lm.cin, S, n, dg, out, f32, out_stride, out_count, gr, flags, s);
-    if (r) return r;
+    RCCHK(caller_in(b, gain, n, b->lm.gg, s, &dg, &host_in));
+    RCCHK(lim_run(b, b->lm.smp, b->lm.cin, S, n, dg, out, f32, out_stride, out_count, gr, flags, s));
     if (host_in) HIPCHK(hipStreamSynchronize(s)); /* the caller's gains are read until here */
     return MP3D_OK;
 }
 
 extern "C" int mp3d_batch_limiter_time(mp3d_batch *b, float *us) {
-    if (!b || !us || !b->timing || !b->lm.tm.timed) return MP3D_E_ARG;
-    return b->lm.tm.elapsed_us(us);
+    return b ? stage_time(b, b->lm.tm, us) : MP3D_E_ARG;
 }

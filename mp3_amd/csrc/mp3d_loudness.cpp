@@ -123,10 +123,7 @@ static void ld_build(int hz, int ch, LdTab &t) {
 
 extern "C" int mp3d_batch_set_loudness(mp3d_batch *b, int on) {
     if (!b || (on && !b->rs.f.hz)) return MP3D_E_ARG;
-    HIPCHK(hipSetDevice(b->device));
-    int r = own_after_last(b);
-    if (r) return r;
-    HIPCHK(hipStreamSynchronize(b->own));
+    RCCHK(set_begin(b));
     mp3d_batch::LoudnessSink &k = b->ld;
     if (!on) {
         k.off();
@@ -135,7 +132,7 @@ extern "C" int mp3d_batch_set_loudness(mp3d_batch *b, int on) {
     std::unique_ptr<LdTab> tab(new LdTab);
     ld_build(b->rs.f.hz, b->rs.ch, *tab);
     const size_t ns = (size_t)b->max_streams;
-    r = k.tab.grow(b, sizeof(LdTab));
+    int r = k.tab.grow(b, sizeof(LdTab));
     if (!r) r = k.st.grow(b, sizeof(LdState) * ns);
     if (!r) r = k.plan.grow(b, sizeof(LdPlan) * ns);
     if (!r) r = k.cin.grow(b, sizeof(int32_t) * ns);
@@ -146,11 +143,9 @@ extern "C" int mp3d_batch_set_loudness(mp3d_batch *b, int on) {
     if (!r) r = hip_rc(hipMemcpyAsync(k.tab, tab.get(), sizeof(LdTab), hipMemcpyHostToDevice, b->own));
     /* setting the sink restarts every stream's loudness state */
     if (!r) r = hip_rc(hipMemsetAsync(k.st, 0, sizeof(LdState) * ns, b->own));
-    if (!r) r = hip_rc(hipStreamSynchronize(b->own)); /* (tab is read until here) */
-    if (r) k.off();
+    r = set_end(b, k, r); /* (tab is read until here) */
     k.on = !r;
     k.H = r ? 0 : tab->H;
-    k.tm.timed = false;
     return r;
 }
 
@@ -164,13 +159,15 @@ static long long ld_bound(long long S, int H) { return (H - 1 + S) / H; }
 static int ld_run(mp3d_batch *b, const float *dsmp, const int32_t *dcin, long long sstride, int n, float *blocks,
                   long long block_stride, int *block_count, float *peak, int flags, hipStream_t s) {
     mp3d_batch::LoudnessSink &k = b->ld;
-    const bool out_dev = is_device_ptr(blocks, b->device), cnt_dev = is_device_ptr(block_count, b->device);
-    const bool pk_dev = peak && is_device_ptr(peak, b->device);
+    const bool out_dev = is_device_ptr(blocks, b->device);
     const long long stride = std::min(block_stride, ld_bound(sstride, k.H));
     const long long tiles = std::max<long long>(1, (sstride + MP3D_LD_TILE - 1) / MP3D_LD_TILE);
     if (tiles * n > 0x7fffffffLL) return MP3D_E_CAPACITY;
     if (out_dev && (uintptr_t)blocks % sizeof(float)) return MP3D_E_ARG;
-    if (pk_dev && (uintptr_t)peak % sizeof(float)) return MP3D_E_ARG;
+    CallerOut<int32_t> cnt;
+    CallerOut<float> pk;
+    RCCHK(cnt.pick(b, (int32_t *)block_count, k.cnt));
+    RCCHK(pk.pick(b, peak, k.pk));
     const size_t nt = (size_t)n * (size_t)tiles;
     int r = MP3D_OK;
     if (!out_dev) r = k.out.grow(b, sizeof(float) * (size_t)stride * n + 16);
@@ -179,40 +176,28 @@ static int ld_run(mp3d_batch *b, const float *dsmp, const int32_t *dcin, long lo
     if (!r) r = k.part.grow(b, sizeof(double) * MP3D_LD_TILE_BLOCKS * nt);
     if (!r) r = k.tpeak.grow(b, sizeof(float) * nt);
     if (r) return r;
-    float *dout = out_dev ? blocks : k.out.p;
-    int32_t *dcnt = cnt_dev ? (int32_t *)block_count : k.cnt.p;
-    float *dpk = pk_dev ? peak : k.pk.p;
-    if (b->timing) HIPCHK(k.tm.begin(s));
-    if (b->poison) launch_lds_poison(g_dev[b->device].n_cu, s);
-    launch_loudness(dsmp, dcin, k.st, k.plan, k.tab, k.H, b->rs.ch, k.tz, k.entry, k.part, k.tpeak, k.endst, dout, dcnt,
-                    dpk, n, sstride, out_dev ? block_stride : stride, (int)tiles, (flags & MP3D_PACK_FLUSH) ? 1 : 0, s);
-    if (b->timing) HIPCHK(k.tm.end(s));
-    HIPCHK(hipGetLastError());
-    if (peak && !pk_dev) {
-        HIPCHK(hipMemcpyAsync(peak, dpk, sizeof(float) * n, hipMemcpyDefault, s));
+    float *dout = out_dev ? blocks : (float *)k.out.p;
+    RCCHK(stage_launch(b, &k.tm, s, [&] {
+        launch_loudness(dsmp, dcin, k.st, k.plan, k.tab, k.H, b->rs.ch, k.tz, k.entry, k.part, k.tpeak, k.endst, dout,
+                        cnt.dev, pk.dev ? pk.dev : k.pk.p, n, sstride, out_dev ? block_stride : stride, (int)tiles,
+                        (flags & MP3D_PACK_FLUSH) ? 1 : 0, s);
+    }));
+    if (pk.host) {
+        HIPCHK(pk.copy_back(n, s));
         HIPCHK(hipStreamSynchronize(s));
     }
-    return deliver_rows(s, n, sizeof(float), dout, stride, blocks, block_stride, dcnt, block_count, out_dev, cnt_dev);
+    return deliver_rows(s, n, sizeof(float), dout, stride, blocks, block_stride, cnt.dev, block_count, out_dev,
+                        !cnt.host);
 }
 
 extern "C" int mp3d_batch_decode_loudness(mp3d_batch *b, const uint8_t *frames, const uint64_t *offsets,
                                           const uint32_t *sizes, int n, int F, float *blocks, long long block_stride,
                                           int *block_count, float *peak, int flags, mp3d_frame_info *infos,
                                           void *hip_stream) {
-    if (!b || !b->ld.on || !blocks || !block_count || block_stride < 0 ||
-        (flags & ~(MP3D_PACK_FLUSH | MP3D_PACK_GAPLESS)))
-        return MP3D_E_ARG;
-    if (!frames || !offsets || !sizes || n <= 0 || F <= 0) return MP3D_E_ARG;
-    if (n > b->max_streams || F > b->max_frames) return MP3D_E_CAPACITY;
-    HIPCHK(hipSetDevice(b->device));
-    /* the packed call into the handle's own samples: a stride no stream can
-     * exceed, counts on the device, so it only queues work */
-    const long long S = mp3d_packed_max_samples(b->rs.f.hz, F, 0);
-    int r = b->ld.smp.grow(b, sizeof(float) * (size_t)S * b->rs.ch * n);
-    if (r) return r;
-    r = mp3d_batch_decode_packed(b, frames, offsets, sizes, n, F, b->ld.smp, 1, S, b->ld.cin, flags, infos, hip_stream);
-    if (r) return r;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : b->own;
+    if (!b || !b->ld.on || !blocks || !block_count || block_stride < 0) return MP3D_E_ARG;
+    long long S;
+    hipStream_t s;
+    RCCHK(decode_to_stage(b, b->ld, frames, offsets, sizes, n, F, flags, infos, hip_stream, &S, &s));
     CallEnd done{b, s};
     return ld_run(b, b->ld.smp, b->ld.cin, S, n, blocks, block_stride, block_count, peak, flags, s);
 }
@@ -228,29 +213,14 @@ extern "C" int mp3d_batch_loudness(mp3d_batch *b, const float *samples, long lon
     if (sample_stride > 0x7fffffffLL) return MP3D_E_ARG; /* counts are int */
     HIPCHK(hipSetDevice(b->device));
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : b->own;
-    int r = call_begin(b, s);
-    if (r) return r;
+    RCCHK(call_begin(b, s));
     CallEnd done{b, s};
-    const float *dsmp = samples;
-    const int32_t *dcin = (const int32_t *)counts;
+    const float *dsmp;
+    const int32_t *dcin;
     bool host_in = false;
-    const size_t row = sizeof(float) * (size_t)sample_stride * b->rs.ch;
-    if (sample_stride && !is_device_ptr(samples, b->device)) {
-        r = b->ld.smp.grow(b, row * n);
-        if (r) return r;
-        HIPCHK(hipMemcpyAsync(b->ld.smp, samples, row * n, hipMemcpyDefault, s));
-        dsmp = b->ld.smp;
-        host_in = true;
-    } else if (sample_stride && (uintptr_t)samples % sizeof(float)) {
-        return MP3D_E_ARG;
-    }
-    if (!is_device_ptr(counts, b->device)) {
-        HIPCHK(hipMemcpyAsync(b->ld.cin, counts, sizeof(int32_t) * n, hipMemcpyDefault, s));
-        dcin = b->ld.cin;
-        host_in = true;
-    }
-    r = ld_run(b, dsmp, dcin, sample_stride, n, blocks, block_stride, block_count, peak, flags, s);
-    if (r) return r;
+    const size_t frame = sizeof(float) * b->rs.ch;
+    RCCHK(stage_inputs(b, b->ld, samples, sample_stride, frame, counts, n, s, &dsmp, &dcin, &host_in));
+    RCCHK(ld_run(b, dsmp, dcin, sample_stride, n, blocks, block_stride, block_count, peak, flags, s));
     if (host_in) HIPCHK(hipStreamSynchronize(s)); /* the caller's host arrays are read until here */
     return MP3D_OK;
 }
@@ -262,38 +232,30 @@ extern "C" int mp3d_batch_loudness_integrated(mp3d_batch *b, const float *blocks
     if (n > b->max_streams) return MP3D_E_CAPACITY;
     HIPCHK(hipSetDevice(b->device));
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : b->own;
-    int r = call_begin(b, s);
-    if (r) return r;
+    RCCHK(call_begin(b, s));
     CallEnd done{b, s};
     mp3d_batch::LoudnessSink &k = b->ld;
+    /* a host caller's rows are staged in out, their counts in cnt */
     const float *dz = blocks;
-    const int32_t *dc = (const int32_t *)counts;
-    const bool lu_dev = is_device_ptr(lufs, b->device);
-    bool host = !lu_dev;
+    const int32_t *dc;
+    bool host = false;
     if (block_stride && !is_device_ptr(blocks, b->device)) {
-        r = k.out.grow(b, sizeof(float) * (size_t)block_stride * n + 16);
-        if (r) return r;
+        RCCHK(k.out.grow(b, sizeof(float) * (size_t)block_stride * n + 16));
         HIPCHK(hipMemcpyAsync(k.out, blocks, sizeof(float) * (size_t)block_stride * n, hipMemcpyDefault, s));
-        dz = k.out;
+        dz = (const float *)k.out.p;
         host = true;
     } else if (block_stride && (uintptr_t)blocks % sizeof(float)) {
         return MP3D_E_ARG;
     }
-    if (!is_device_ptr(counts, b->device)) {
-        HIPCHK(hipMemcpyAsync(k.cnt, counts, sizeof(int32_t) * n, hipMemcpyDefault, s));
-        dc = k.cnt;
-        host = true;
-    }
-    if (lu_dev && (uintptr_t)lufs % sizeof(float)) return MP3D_E_ARG;
-    if (b->poison) launch_lds_poison(g_dev[b->device].n_cu, s);
-    launch_loudness_gate(dz, block_stride, dc, lu_dev ? lufs : k.lu.p, n, s);
-    HIPCHK(hipGetLastError());
-    if (!lu_dev) HIPCHK(hipMemcpyAsync(lufs, k.lu, sizeof(float) * n, hipMemcpyDefault, s));
-    if (host) HIPCHK(hipStreamSynchronize(s));
+    RCCHK(caller_in(b, (const int32_t *)counts, n, k.cnt, s, &dc, &host));
+    CallerOut<float> lu;
+    RCCHK(lu.pick(b, lufs, k.lu));
+    RCCHK(stage_launch(b, nullptr, s, [&] { launch_loudness_gate(dz, block_stride, dc, lu.dev, n, s); }));
+    HIPCHK(lu.copy_back(n, s));
+    if (host || lu.host) HIPCHK(hipStreamSynchronize(s));
     return MP3D_OK;
 }
 
 extern "C" int mp3d_batch_loudness_time(mp3d_batch *b, float *us) {
-    if (!b || !us || !b->timing || !b->ld.tm.timed) return MP3D_E_ARG;
-    return b->ld.tm.elapsed_us(us);
+    return b ? stage_time(b, b->ld.tm, us) : MP3D_E_ARG;
 }

@@ -46,19 +46,16 @@ extern "C" long long mp3d_truepeak_filter(float *taps, size_t cap) {
 
 extern "C" int mp3d_batch_set_true_peak(mp3d_batch *b, int on) {
     if (!b || (on && !b->rs.f.hz)) return MP3D_E_ARG;
-    HIPCHK(hipSetDevice(b->device));
-    int r = own_after_last(b);
-    if (r) return r;
-    HIPCHK(hipStreamSynchronize(b->own));
-    mp3d_batch::NormalizeSink &k = b->nm;
+    RCCHK(set_begin(b));
+    mp3d_batch::TruePeakTap &k = b->nm;
     if (!on) {
-        k.tap_off();
+        k.off();
         return MP3D_OK;
     }
     float taps[MP3D_TP_R * MP3D_TP_TAPS];
     tp_design(taps);
     const size_t ns = (size_t)b->max_streams;
-    r = k.taps.grow(b, sizeof(taps));
+    int r = k.taps.grow(b, sizeof(taps));
     if (!r) r = k.st.grow(b, sizeof(TpState) * ns);
     if (!r) r = k.plan.grow(b, sizeof(TpPlan) * ns);
     if (!r) r = k.cin.grow(b, sizeof(int32_t) * ns);
@@ -66,10 +63,8 @@ extern "C" int mp3d_batch_set_true_peak(mp3d_batch *b, int on) {
     if (!r) r = hip_rc(hipMemcpyAsync(k.taps, taps, sizeof(taps), hipMemcpyHostToDevice, b->own));
     /* setting the tap restarts every stream's true-peak state */
     if (!r) r = hip_rc(hipMemsetAsync(k.st, 0, sizeof(TpState) * ns, b->own));
-    if (!r) r = hip_rc(hipStreamSynchronize(b->own)); /* (taps is read until here) */
-    if (r) k.tap_off();
+    r = set_end(b, k, r); /* (taps is read until here) */
     k.on = !r;
-    k.tm.timed = false;
     return r;
 }
 
@@ -79,23 +74,19 @@ extern "C" int mp3d_batch_set_true_peak(mp3d_batch *b, int on) {
  * done. */
 static int tp_run(mp3d_batch *b, const float *dsmp, const int32_t *dcin, long long sstride, int n, float *tpeak,
                   int flags, hipStream_t s) {
-    mp3d_batch::NormalizeSink &k = b->nm;
-    const bool tp_dev = is_device_ptr(tpeak, b->device);
+    mp3d_batch::TruePeakTap &k = b->nm;
     /* a call emits at most its samples plus the POST a flush releases */
     const long long tiles = std::max<long long>(1, (sstride + MP3D_TP_POST + MP3D_TP_TILE - 1) / MP3D_TP_TILE);
     if (tiles * n > 0x7fffffffLL) return MP3D_E_CAPACITY;
-    if (tp_dev && (uintptr_t)tpeak % sizeof(float)) return MP3D_E_ARG;
-    const int r = k.tile.grow(b, sizeof(float) * (size_t)n * (size_t)tiles);
-    if (r) return r;
-    float *dtp = tp_dev ? tpeak : k.tp.p;
-    if (b->timing) HIPCHK(k.tm.begin(s));
-    if (b->poison) launch_lds_poison(g_dev[b->device].n_cu, s);
-    launch_true_peak(dsmp, dcin, k.st, k.plan, k.taps, k.tile, dtp, n, sstride, b->rs.ch, (int)tiles,
-                     (flags & MP3D_PACK_FLUSH) ? 1 : 0, s);
-    if (b->timing) HIPCHK(k.tm.end(s));
-    HIPCHK(hipGetLastError());
-    if (!tp_dev) {
-        HIPCHK(hipMemcpyAsync(tpeak, dtp, sizeof(float) * n, hipMemcpyDefault, s));
+    CallerOut<float> tp;
+    RCCHK(tp.pick(b, tpeak, k.tp));
+    RCCHK(k.tile.grow(b, sizeof(float) * (size_t)n * (size_t)tiles));
+    RCCHK(stage_launch(b, &k.tm, s, [&] {
+        launch_true_peak(dsmp, dcin, k.st, k.plan, k.taps, k.tile, tp.dev, n, sstride, b->rs.ch, (int)tiles,
+                         (flags & MP3D_PACK_FLUSH) ? 1 : 0, s);
+    }));
+    if (tp.host) {
+        HIPCHK(tp.copy_back(n, s));
         HIPCHK(hipStreamSynchronize(s));
     }
     return MP3D_OK;
@@ -113,29 +104,14 @@ extern "C" int mp3d_batch_true_peak(mp3d_batch *b, const float *samples, long lo
     if (sample_stride > TP_MAX_STRIDE) return MP3D_E_ARG;
     HIPCHK(hipSetDevice(b->device));
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : b->own;
-    int r = call_begin(b, s);
-    if (r) return r;
+    RCCHK(call_begin(b, s));
     CallEnd done{b, s};
-    const float *dsmp = samples;
-    const int32_t *dcin = (const int32_t *)counts;
+    const float *dsmp;
+    const int32_t *dcin;
     bool host_in = false;
-    const size_t row = sizeof(float) * (size_t)sample_stride * b->rs.ch;
-    if (sample_stride && !is_device_ptr(samples, b->device)) {
-        r = b->nm.smp.grow(b, row * n);
-        if (r) return r;
-        HIPCHK(hipMemcpyAsync(b->nm.smp, samples, row * n, hipMemcpyDefault, s));
-        dsmp = b->nm.smp;
-        host_in = true;
-    } else if (sample_stride && (uintptr_t)samples % sizeof(float)) {
-        return MP3D_E_ARG;
-    }
-    if (!is_device_ptr(counts, b->device)) {
-        HIPCHK(hipMemcpyAsync(b->nm.cin, counts, sizeof(int32_t) * n, hipMemcpyDefault, s));
-        dcin = b->nm.cin;
-        host_in = true;
-    }
-    r = tp_run(b, dsmp, dcin, sample_stride, n, tpeak, flags, s);
-    if (r) return r;
+    const size_t frame = sizeof(float) * b->rs.ch;
+    RCCHK(stage_inputs(b, b->nm, samples, sample_stride, frame, counts, n, s, &dsmp, &dcin, &host_in));
+    RCCHK(tp_run(b, dsmp, dcin, sample_stride, n, tpeak, flags, s));
     if (host_in) HIPCHK(hipStreamSynchronize(s)); /* the caller's host arrays are read until here */
     return MP3D_OK;
 }
@@ -147,38 +123,16 @@ extern "C" int mp3d_batch_decode_measure(mp3d_batch *b, const uint8_t *frames, c
     if (!b || !b->ld.on || !b->nm.on || !tpeak) return MP3D_E_ARG;
     /* the loudness call decodes into the handle's samples and counts and
      * leaves them there: the tap runs on the same ones, after it */
-    int r = mp3d_batch_decode_loudness(b, frames, offsets, sizes, n, F, blocks, block_stride, block_count, peak, flags,
-                                       infos, hip_stream);
-    if (r) return r;
+    RCCHK(mp3d_batch_decode_loudness(b, frames, offsets, sizes, n, F, blocks, block_stride, block_count, peak, flags,
+                                     infos, hip_stream));
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : b->own;
-    r = call_begin(b, s);
-    if (r) return r;
+    RCCHK(call_begin(b, s));
     CallEnd done{b, s};
-    const long long S = mp3d_packed_max_samples(b->rs.f.hz, F, 0);
-    return tp_run(b, b->ld.smp, b->ld.cin, S, n, tpeak, flags, s);
+    return tp_run(b, b->ld.smp, b->ld.cin, stage_stride(b, F), n, tpeak, flags, s);
 }
 
 extern "C" int mp3d_batch_true_peak_time(mp3d_batch *b, float *us) {
-    if (!b || !us || !b->timing || !b->nm.tm.timed) return MP3D_E_ARG;
-    return b->nm.tm.elapsed_us(us);
-}
-
-/* A caller's n-element array for a kernel to read on stream s: itself when it
- * is device memory (element-aligned, else MP3D_E_ARG), else a copy in
- * `stage`; *host is set when the caller's host memory is read */
-template <class T>
-static int ga_input(mp3d_batch *b, const T *p, int n, DevBuf<T> &stage, hipStream_t s, const T **dev, bool *host) {
-    if (is_device_ptr(p, b->device)) {
-        if ((uintptr_t)p % sizeof(T)) return MP3D_E_ARG;
-        *dev = p;
-        return MP3D_OK;
-    }
-    const int r = stage.grow(b, sizeof(T) * (size_t)b->max_streams);
-    if (r) return r;
-    HIPCHK(hipMemcpyAsync(stage.p, p, sizeof(T) * (size_t)n, hipMemcpyDefault, s));
-    *dev = stage.p;
-    *host = true;
-    return MP3D_OK;
+    return b ? stage_time(b, b->nm.tm, us) : MP3D_E_ARG;
 }
 
 extern "C" int mp3d_batch_normalize_gain(mp3d_batch *b, const float *lufs, const float *tpeak, int n,
@@ -187,26 +141,20 @@ extern "C" int mp3d_batch_normalize_gain(mp3d_batch *b, const float *lufs, const
     if (n > b->max_streams) return MP3D_E_CAPACITY;
     HIPCHK(hipSetDevice(b->device));
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : b->own;
-    int r = call_begin(b, s);
-    if (r) return r;
+    RCCHK(call_begin(b, s));
     CallEnd done{b, s};
-    mp3d_batch::NormalizeSink &k = b->nm;
-    const float *dl = nullptr, *dt = nullptr;
+    mp3d_batch::GainCalls &k = b->ga;
+    const float *dl, *dt;
     bool host = false;
-    r = ga_input(b, lufs, n, k.lu, s, &dl, &host);
-    if (!r && tpeak) r = ga_input(b, tpeak, n, k.gtp, s, &dt, &host);
-    if (r) return r;
-    const bool gn_dev = is_device_ptr(gain, b->device);
-    if (gn_dev && (uintptr_t)gain % sizeof(float)) return MP3D_E_ARG;
-    if (!gn_dev) {
-        r = k.gain.grow(b, sizeof(float) * (size_t)b->max_streams);
-        if (r) return r;
-    }
-    if (b->poison) launch_lds_poison(g_dev[b->device].n_cu, s);
-    launch_gain_calc(dl, dt, gn_dev ? gain : k.gain.p, n, target_lufs, pow(10.0, max_dbtp / 20.0), s);
-    HIPCHK(hipGetLastError());
-    if (!gn_dev) HIPCHK(hipMemcpyAsync(gain, k.gain, sizeof(float) * n, hipMemcpyDefault, s));
-    if (host || !gn_dev) HIPCHK(hipStreamSynchronize(s));
+    RCCHK(caller_in(b, lufs, n, k.lu, s, &dl, &host));
+    RCCHK(caller_in(b, tpeak, n, k.gtp, s, &dt, &host));
+    CallerOut<float> gn;
+    RCCHK(gn.pick(b, gain, k.gain));
+    RCCHK(stage_launch(b, nullptr, s, [&] {
+        launch_gain_calc(dl, dt, gn.dev, n, target_lufs, pow(10.0, max_dbtp / 20.0), s);
+    }));
+    HIPCHK(gn.copy_back(n, s));
+    if (host || gn.host) HIPCHK(hipStreamSynchronize(s));
     return MP3D_OK;
 }
 
@@ -226,35 +174,24 @@ extern "C" int mp3d_batch_apply_gain(mp3d_batch *b, const float *samples, long l
     if (out_dev && (uintptr_t)out % (eb * oc)) return MP3D_E_ARG;
     HIPCHK(hipSetDevice(b->device));
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : b->own;
-    int r = call_begin(b, s);
-    if (r) return r;
+    RCCHK(call_begin(b, s));
     CallEnd done{b, s};
-    mp3d_batch::NormalizeSink &k = b->nm;
-    const float *dsmp = samples, *dg = nullptr;
-    const int32_t *dcin = nullptr;
+    mp3d_batch::GainCalls &k = b->ga;
+    const float *dsmp, *dg;
+    const int32_t *dcin;
     bool host_in = false;
-    const size_t row = sizeof(float) * (size_t)sample_stride * oc;
-    if (sample_stride && !is_device_ptr(samples, b->device)) {
-        r = k.gsmp.grow(b, row * n);
-        if (r) return r;
-        HIPCHK(hipMemcpyAsync(k.gsmp, samples, row * n, hipMemcpyDefault, s));
-        dsmp = k.gsmp;
-        host_in = true;
-    } else if (sample_stride && (uintptr_t)samples % sizeof(float)) {
-        return MP3D_E_ARG;
-    }
-    r = ga_input(b, (const int32_t *)counts, n, k.gcin, s, &dcin, &host_in);
-    if (!r) r = ga_input(b, gain, n, k.gg, s, &dg, &host_in);
-    if (!r) r = k.ccnt.grow(b, sizeof(int32_t) * (size_t)b->max_streams);
-    if (!r && !out_dev) r = k.out.grow(b, eb * oc * (size_t)sample_stride * n + 16);
-    if (r) return r;
+    RCCHK(stage_inputs(b, k, samples, sample_stride, sizeof(float) * oc, counts, n, s, &dsmp, &dcin, &host_in));
+    RCCHK(caller_in(b, gain, n, k.gg, s, &dg, &host_in));
+    /* cnt: each stream's count clamped to the stride */
+    RCCHK(k.cnt.grow(b, sizeof(int32_t) * (size_t)b->max_streams));
+    if (!out_dev) RCCHK(k.out.grow(b, eb * oc * (size_t)sample_stride * n + 16));
     void *dout = out_dev ? out : k.out.p;
-    if (b->poison) launch_lds_poison(g_dev[b->device].n_cu, s);
-    launch_gain_apply(dsmp, dcin, dg, dout, k.ccnt, f32 != 0, oc, n, sample_stride, (int)chunks, s);
-    HIPCHK(hipGetLastError());
+    RCCHK(stage_launch(b, nullptr, s, [&] {
+        launch_gain_apply(dsmp, dcin, dg, dout, k.cnt, f32 != 0, oc, n, sample_stride, (int)chunks, s);
+    }));
     /* a host out: each stream's own rows, by its clamped count */
-    r = deliver_rows(s, n, eb * oc, dout, sample_stride, out, sample_stride, k.ccnt, nullptr, out_dev, true);
-    if (r) return r;
+    RCCHK(deliver_rows(s, n, eb * oc, dout, sample_stride, out, sample_stride, k.cnt, nullptr, out_dev, true));
     if (host_in) HIPCHK(hipStreamSynchronize(s)); /* the caller's host arrays are read until here */
     return MP3D_OK;
 }
+

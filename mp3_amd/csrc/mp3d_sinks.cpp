@@ -154,22 +154,15 @@ int RsFilters::upload(const mp3d_batch *b, int out_hz, int out_channels, hipStre
 extern "C" int mp3d_batch_set_output(mp3d_batch *b, int out_hz, int out_channels) {
     if (!b) return MP3D_E_ARG;
     if (out_hz != 0 && (rs_rate_index(out_hz) < 0 || (out_channels != 1 && out_channels != 2))) return MP3D_E_ARG;
-    HIPCHK(hipSetDevice(b->device));
-    int r = own_after_last(b);
-    if (r) return r;
-    HIPCHK(hipStreamSynchronize(b->own));
-    b->ft.off(); /* the feature sink reads this sink's format: off with any change of it */
-    b->ld.off(); /* and so does the loudness sink */
-    b->nm.off(); /* and the true-peak tap and the gain calls */
-    b->sx.off(); /* and the tempo sink */
-    b->lm.off(); /* and the limiter */
+    RCCHK(set_begin(b));
+    stages_off(b);
     mp3d_batch::PackedSink &k = b->rs;
     if (out_hz == 0) {
         k.off();
         return MP3D_OK;
     }
     const size_t ns = (size_t)b->max_streams;
-    r = k.st.grow(b, sizeof(RsState) * ns);
+    int r = k.st.grow(b, sizeof(RsState) * ns);
     if (!r) r = k.plan.grow(b, sizeof(RsPlan) * ns);
     if (!r) r = k.cnt.grow(b, sizeof(int32_t) * ns);
     /* a change of the output format restarts every stream's resampler */
@@ -234,20 +227,46 @@ extern "C" int mp3d_batch_decode_packed(mp3d_batch *b, const uint8_t *frames, co
     const mp3d_frame_info *dinf = infos && is_device_ptr(infos, b->device) ? infos : b->d_infos.p;
     void *dout = out_dev ? out : k.out.p;
     int32_t *dcnt = cnt_dev ? (int32_t *)out_count : k.cnt.p;
-    if (b->timing) HIPCHK(k.tm.begin(s));
-    if (b->poison) launch_lds_poison(g_dev[b->device].n_cu, s);
-    launch_resample(k.rows, dinf, k.st, b->st, k.f.dcfg, oc, k.f.tab, k.plan, k.prefix, dout, f32 != 0, dcnt, n, F,
-                    out_dev ? out_stride : stride, (int)tiles, (flags & MP3D_PACK_FLUSH) ? 1 : 0,
-                    (flags & MP3D_PACK_GAPLESS) ? 1 : 0, s);
-    if (b->timing) HIPCHK(k.tm.end(s));
-    HIPCHK(hipGetLastError());
+    RCCHK(stage_launch(b, &k.tm, s, [&] {
+        launch_resample(k.rows, dinf, k.st, b->st, k.f.dcfg, oc, k.f.tab, k.plan, k.prefix, dout, f32 != 0, dcnt, n, F,
+                        out_dev ? out_stride : stride, (int)tiles, (flags & MP3D_PACK_FLUSH) ? 1 : 0,
+                        (flags & MP3D_PACK_GAPLESS) ? 1 : 0, s);
+    }));
     /* the caller's stride is its own, the staging buffer's is `stride` */
     return deliver_rows(s, n, eb * oc, dout, stride, out, out_stride, dcnt, out_count, out_dev, cnt_dev);
 }
 
 extern "C" int mp3d_batch_resample_time(mp3d_batch *b, float *us) {
-    if (!b || !us || !b->timing || !b->rs.tm.timed) return MP3D_E_ARG;
-    return b->rs.tm.elapsed_us(us);
+    return b ? stage_time(b, b->rs.tm, us) : MP3D_E_ARG;
+}
+
+int mp3d::stage_inputs(mp3d_batch *b, mp3d_batch::Stage &k, const float *samples, long long stride, size_t frame,
+                       const int *counts, int n, hipStream_t s, const float **dsmp, const int32_t **dcin, bool *host) {
+    const size_t bytes = frame * (size_t)stride * n;
+    *dsmp = samples;
+    if (stride && !is_device_ptr(samples, b->device)) {
+        RCCHK(k.smp.grow(b, bytes));
+        HIPCHK(hipMemcpyAsync(k.smp, samples, bytes, hipMemcpyDefault, s));
+        *dsmp = k.smp;
+        *host = true;
+    } else if (stride && (uintptr_t)samples % sizeof(float)) {
+        return MP3D_E_ARG;
+    }
+    return caller_in(b, (const int32_t *)counts, n, k.cin, s, dcin, host);
+}
+
+int mp3d::decode_to_stage(mp3d_batch *b, mp3d_batch::Stage &k, const uint8_t *frames, const uint64_t *offsets,
+                          const uint32_t *sizes, int n, int F, int flags, mp3d_frame_info *infos, void *hip_stream,
+                          long long *S, hipStream_t *s) {
+    if (flags & ~(MP3D_PACK_FLUSH | MP3D_PACK_GAPLESS)) return MP3D_E_ARG;
+    if (!frames || !offsets || !sizes || n <= 0 || F <= 0) return MP3D_E_ARG;
+    if (n > b->max_streams || F > b->max_frames) return MP3D_E_CAPACITY;
+    HIPCHK(hipSetDevice(b->device));
+    /* a stride no stream can exceed, counts on the device */
+    *S = stage_stride(b, F);
+    RCCHK(k.smp.grow(b, sizeof(float) * (size_t)*S * b->rs.ch * n));
+    *s = hip_stream ? (hipStream_t)hip_stream : b->own;
+    return mp3d_batch_decode_packed(b, frames, offsets, sizes, n, F, k.smp, 1, *S, k.cin, flags, infos, hip_stream);
 }
 
 /* RsWindow is the head of RsState, r follows it: one strided copy each way */
@@ -274,11 +293,7 @@ extern "C" int mp3d_batch_set_window(mp3d_batch *b, int first, int n, const long
     if (r) return r;
     /* a window restart: the slots' resamplers and fed counts restart with it */
     HIPCHK(hipMemsetAsync(b->rs.st + first, 0, sizeof(RsState) * (size_t)n, s));
-    if (b->ft.st) HIPCHK(hipMemsetAsync(b->ft.st + first, 0, sizeof(FtState) * (size_t)n, s));
-    if (b->ld.st) HIPCHK(hipMemsetAsync(b->ld.st + first, 0, sizeof(LdState) * (size_t)n, s));
-    if (b->nm.st) HIPCHK(hipMemsetAsync(b->nm.st + first, 0, sizeof(TpState) * (size_t)n, s));
-    if (b->sx.st) HIPCHK(hipMemsetAsync(b->sx.st + first, 0, sizeof(StState) * (size_t)n, s));
-    if (b->lm.st) HIPCHK(hipMemsetAsync(b->lm.st + first, 0, sizeof(LimState) * (size_t)n, s));
+    RCCHK(stages_restart(b, first, n, s));
     if (lo)
         HIPCHK(hipMemcpy2DAsync(b->rs.st + first, sizeof(RsState), w.data(), sizeof(RsWindow), sizeof(RsWindow), (size_t)n,
                                 hipMemcpyHostToDevice, s));
@@ -385,20 +400,16 @@ static int ft_build(int n_mels, int flags, FtTab &t) {
 extern "C" int mp3d_batch_set_features(mp3d_batch *b, int n_mels, int flags) {
     if (!b || n_mels < 0 || n_mels > MP3D_FT_MAX_MELS || (flags & ~MP3D_FEAT_LOG10)) return MP3D_E_ARG;
     if (n_mels && (b->rs.f.hz != 16000 || b->rs.ch != 1)) return MP3D_E_ARG;
-    HIPCHK(hipSetDevice(b->device));
-    int r = own_after_last(b);
-    if (r) return r;
-    HIPCHK(hipStreamSynchronize(b->own));
+    RCCHK(set_begin(b));
     mp3d_batch::FeatureSink &k = b->ft;
     if (n_mels == 0) {
         k.off();
         return MP3D_OK;
     }
     FtTab tab;
-    r = ft_build(n_mels, flags, tab);
-    if (r) return r;
+    RCCHK(ft_build(n_mels, flags, tab));
     const size_t ns = (size_t)b->max_streams;
-    r = k.tab.grow(b, sizeof(FtTab));
+    int r = k.tab.grow(b, sizeof(FtTab));
     if (!r) r = k.st.grow(b, sizeof(FtState) * ns);
     if (!r) r = k.plan.grow(b, sizeof(FtPlan) * ns);
     if (!r) r = k.cin.grow(b, sizeof(int32_t) * ns);
@@ -406,10 +417,8 @@ extern "C" int mp3d_batch_set_features(mp3d_batch *b, int n_mels, int flags) {
     if (!r) r = hip_rc(hipMemcpyAsync(k.tab, &tab, sizeof(tab), hipMemcpyHostToDevice, b->own));
     /* a change of the features restarts every stream's feature state */
     if (!r) r = hip_rc(hipMemsetAsync(k.st, 0, sizeof(FtState) * ns, b->own));
-    if (!r) r = hip_rc(hipStreamSynchronize(b->own)); /* (tab is on this stack) */
-    if (r) k.off();
+    r = set_end(b, k, r); /* (tab is on this stack) */
     k.mels = r ? 0 : n_mels;
-    k.tm.timed = false;
     return r;
 }
 
@@ -420,42 +429,31 @@ extern "C" int mp3d_batch_set_features(mp3d_batch *b, int n_mels, int flags) {
 static int ft_run(mp3d_batch *b, const float *dsmp, const int32_t *dcin, long long sstride, int n, float *feat,
                   long long feat_stride, int *feat_count, int flags, hipStream_t s) {
     mp3d_batch::FeatureSink &k = b->ft;
-    const bool out_dev = is_device_ptr(feat, b->device), cnt_dev = is_device_ptr(feat_count, b->device);
+    const bool out_dev = is_device_ptr(feat, b->device);
     /* blocks per stream: enough tiles for the most frames the stride admits */
     const long long stride = std::min(feat_stride, ft_bound(sstride));
     const long long tiles = std::max<long long>(1, (stride + MP3D_FT_TILE - 1) / MP3D_FT_TILE);
     if (tiles * n > 0x7fffffffLL) return MP3D_E_CAPACITY;
     if (out_dev && (uintptr_t)feat % sizeof(float)) return MP3D_E_ARG;
-    int r = MP3D_OK;
-    if (!out_dev) r = k.out.grow(b, sizeof(float) * k.mels * (size_t)stride * n + 16);
-    if (r) return r;
-    float *dout = out_dev ? feat : k.out.p;
-    int32_t *dcnt = cnt_dev ? (int32_t *)feat_count : k.cnt.p;
-    if (b->timing) HIPCHK(k.tm.begin(s));
-    if (b->poison) launch_lds_poison(g_dev[b->device].n_cu, s);
-    launch_features(dsmp, dcin, k.st, k.plan, k.tab, dout, dcnt, n, sstride, out_dev ? feat_stride : stride, (int)tiles,
-                    (flags & MP3D_PACK_FLUSH) ? 1 : 0, s);
-    if (b->timing) HIPCHK(k.tm.end(s));
-    HIPCHK(hipGetLastError());
-    return deliver_rows(s, n, sizeof(float) * k.mels, dout, stride, feat, feat_stride, dcnt, feat_count, out_dev, cnt_dev);
+    CallerOut<int32_t> cnt;
+    RCCHK(cnt.pick(b, (int32_t *)feat_count, k.cnt));
+    if (!out_dev) RCCHK(k.out.grow(b, sizeof(float) * k.mels * (size_t)stride * n + 16));
+    float *dout = out_dev ? feat : (float *)k.out.p;
+    RCCHK(stage_launch(b, &k.tm, s, [&] {
+        launch_features(dsmp, dcin, k.st, k.plan, k.tab, dout, cnt.dev, n, sstride, out_dev ? feat_stride : stride,
+                        (int)tiles, (flags & MP3D_PACK_FLUSH) ? 1 : 0, s);
+    }));
+    return deliver_rows(s, n, sizeof(float) * k.mels, dout, stride, feat, feat_stride, cnt.dev, feat_count, out_dev,
+                        !cnt.host);
 }
 
 extern "C" int mp3d_batch_decode_features(mp3d_batch *b, const uint8_t *frames, const uint64_t *offsets,
                                           const uint32_t *sizes, int n, int F, float *feat, long long feat_stride,
                                           int *feat_count, int flags, mp3d_frame_info *infos, void *hip_stream) {
-    if (!b || !b->ft.mels || !feat || !feat_count || feat_stride < 0 || (flags & ~(MP3D_PACK_FLUSH | MP3D_PACK_GAPLESS)))
-        return MP3D_E_ARG;
-    if (!frames || !offsets || !sizes || n <= 0 || F <= 0) return MP3D_E_ARG;
-    if (n > b->max_streams || F > b->max_frames) return MP3D_E_CAPACITY;
-    HIPCHK(hipSetDevice(b->device));
-    /* the packed call into the handle's own samples: a stride no stream can
-     * exceed, counts on the device, so it only queues work */
-    const long long S = mp3d_packed_max_samples(16000, F, 0);
-    int r = b->ft.smp.grow(b, sizeof(float) * (size_t)S * n);
-    if (r) return r;
-    r = mp3d_batch_decode_packed(b, frames, offsets, sizes, n, F, b->ft.smp, 1, S, b->ft.cin, flags, infos, hip_stream);
-    if (r) return r;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : b->own;
+    if (!b || !b->ft.mels || !feat || !feat_count || feat_stride < 0) return MP3D_E_ARG;
+    long long S;
+    hipStream_t s;
+    RCCHK(decode_to_stage(b, b->ft, frames, offsets, sizes, n, F, flags, infos, hip_stream, &S, &s));
     CallEnd done{b, s};
     return ft_run(b, b->ft.smp, b->ft.cin, S, n, feat, feat_stride, feat_count, flags, s);
 }
@@ -470,33 +468,17 @@ extern "C" int mp3d_batch_features(mp3d_batch *b, const float *samples, long lon
     if (sample_stride > 0x7fffffffLL) return MP3D_E_ARG; /* counts are int */
     HIPCHK(hipSetDevice(b->device));
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : b->own;
-    int r = call_begin(b, s);
-    if (r) return r;
+    RCCHK(call_begin(b, s));
     CallEnd done{b, s};
-    const float *dsmp = samples;
-    const int32_t *dcin = (const int32_t *)counts;
+    const float *dsmp;
+    const int32_t *dcin;
     bool host_in = false;
-    if (sample_stride && !is_device_ptr(samples, b->device)) {
-        r = b->ft.smp.grow(b, sizeof(float) * (size_t)sample_stride * n);
-        if (r) return r;
-        HIPCHK(hipMemcpyAsync(b->ft.smp, samples, sizeof(float) * (size_t)sample_stride * n, hipMemcpyDefault, s));
-        dsmp = b->ft.smp;
-        host_in = true;
-    } else if (sample_stride && (uintptr_t)samples % sizeof(float)) {
-        return MP3D_E_ARG;
-    }
-    if (!is_device_ptr(counts, b->device)) {
-        HIPCHK(hipMemcpyAsync(b->ft.cin, counts, sizeof(int32_t) * n, hipMemcpyDefault, s));
-        dcin = b->ft.cin;
-        host_in = true;
-    }
-    r = ft_run(b, dsmp, dcin, sample_stride, n, feat, feat_stride, feat_count, flags, s);
-    if (r) return r;
+    RCCHK(stage_inputs(b, b->ft, samples, sample_stride, sizeof(float), counts, n, s, &dsmp, &dcin, &host_in));
+    RCCHK(ft_run(b, dsmp, dcin, sample_stride, n, feat, feat_stride, feat_count, flags, s));
     if (host_in) HIPCHK(hipStreamSynchronize(s)); /* the caller's host arrays are read until here */
     return MP3D_OK;
 }
 
 extern "C" int mp3d_batch_feature_time(mp3d_batch *b, float *us) {
-    if (!b || !us || !b->timing || !b->ft.tm.timed) return MP3D_E_ARG;
-    return b->ft.tm.elapsed_us(us);
+    return b ? stage_time(b, b->ft.tm, us) : MP3D_E_ARG;
 }

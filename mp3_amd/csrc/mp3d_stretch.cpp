@@ -41,10 +41,7 @@ extern "C" long long mp3d_stretch_max_samples(int out_hz, long long in_samples, 
 
 extern "C" int mp3d_batch_set_stretch(mp3d_batch *b, int on) {
     if (!b || (on && !b->rs.f.hz)) return MP3D_E_ARG;
-    HIPCHK(hipSetDevice(b->device));
-    int r = own_after_last(b);
-    if (r) return r;
-    HIPCHK(hipStreamSynchronize(b->own));
+    RCCHK(set_begin(b));
     mp3d_batch::StretchSink &k = b->sx;
     if (!on) {
         k.off();
@@ -56,7 +53,7 @@ extern "C" int mp3d_batch_set_stretch(mp3d_batch *b, int on) {
     st_window(H, w);
     const size_t ns = (size_t)b->max_streams;
     std::vector<int32_t> one(2 * ns, 1); /* every slot at tempo 1/1 */
-    r = k.w.grow(b, sizeof(float) * MP3D_ST_HMAX);
+    int r = k.w.grow(b, sizeof(float) * MP3D_ST_HMAX);
     if (!r) r = k.st.grow(b, sizeof(StState) * ns);
     if (!r) r = k.plan.grow(b, sizeof(StPlan) * ns);
     if (!r) r = k.tempo.grow(b, sizeof(int32_t) * 2 * ns);
@@ -66,11 +63,9 @@ extern "C" int mp3d_batch_set_stretch(mp3d_batch *b, int on) {
     if (!r) r = hip_rc(hipMemcpyAsync(k.tempo, one.data(), sizeof(int32_t) * 2 * ns, hipMemcpyHostToDevice, b->own));
     /* setting the sink restarts every stream's stretch state */
     if (!r) r = hip_rc(hipMemsetAsync(k.st, 0, sizeof(StState) * ns, b->own));
-    if (!r) r = hip_rc(hipStreamSynchronize(b->own)); /* (w and one are read until here) */
-    if (r) k.off();
+    r = set_end(b, k, r); /* (w and one are read until here) */
     k.on = !r;
     k.H = r ? 0 : H;
-    k.tm.timed = false;
     return r;
 }
 
@@ -102,25 +97,20 @@ static int st_run(mp3d_batch *b, const float *dsmp, const int32_t *dcin, long lo
                   long long out_stride, int *out_count, int flags, hipStream_t s) {
     mp3d_batch::StretchSink &k = b->sx;
     const int oc = b->rs.ch;
-    const bool out_dev = is_device_ptr(out, b->device), cnt_dev = is_device_ptr(out_count, b->device);
+    const bool out_dev = is_device_ptr(out, b->device);
     /* (the alignment rule of mp3d_batch_apply_gain's out) */
     if (out_dev && (uintptr_t)out % (sizeof(float) * oc)) return MP3D_E_ARG;
-    if (cnt_dev && (uintptr_t)out_count % sizeof(int32_t)) return MP3D_E_ARG;
+    CallerOut<int32_t> cnt;
+    RCCHK(cnt.pick(b, (int32_t *)out_count, k.cnt));
     /* no call emits more than the bound at the slowest tempo */
     const long long stride = std::min(out_stride, st_bound(k.H, sstride, 1, 2));
-    if (!out_dev) {
-        const int r = k.out.grow(b, sizeof(float) * oc * (size_t)stride * n + 16);
-        if (r) return r;
-    }
-    float *dout = out_dev ? out : k.out.p;
-    int32_t *dcnt = cnt_dev ? (int32_t *)out_count : k.cnt.p;
-    if (b->timing) HIPCHK(k.tm.begin(s));
-    if (b->poison) launch_lds_poison(g_dev[b->device].n_cu, s);
-    launch_stretch(dsmp, dcin, k.st, k.tempo, k.plan, k.w, dout, dcnt, n, sstride, out_dev ? out_stride : stride, k.H, oc,
-                   (flags & MP3D_PACK_FLUSH) ? 1 : 0, s);
-    if (b->timing) HIPCHK(k.tm.end(s));
-    HIPCHK(hipGetLastError());
-    return deliver_rows(s, n, sizeof(float) * oc, dout, stride, out, out_stride, dcnt, out_count, out_dev, cnt_dev);
+    if (!out_dev) RCCHK(k.out.grow(b, sizeof(float) * oc * (size_t)stride * n + 16));
+    float *dout = out_dev ? out : (float *)k.out.p;
+    RCCHK(stage_launch(b, &k.tm, s, [&] {
+        launch_stretch(dsmp, dcin, k.st, k.tempo, k.plan, k.w, dout, cnt.dev, n, sstride, out_dev ? out_stride : stride,
+                       k.H, oc, (flags & MP3D_PACK_FLUSH) ? 1 : 0, s);
+    }));
+    return deliver_rows(s, n, sizeof(float) * oc, dout, stride, out, out_stride, cnt.dev, out_count, out_dev, !cnt.host);
 }
 
 extern "C" int mp3d_batch_stretch(mp3d_batch *b, const float *samples, long long sample_stride, const int *counts, int n,
@@ -131,37 +121,19 @@ extern "C" int mp3d_batch_stretch(mp3d_batch *b, const float *samples, long long
     if ((!samples && sample_stride) || n <= 0) return MP3D_E_ARG;
     if (n > b->max_streams) return MP3D_E_CAPACITY;
     if (sample_stride > 0x7fffffffLL || out_stride > 0x7fffffffLL) return MP3D_E_ARG; /* counts are int */
-    const size_t row = sizeof(float) * (size_t)sample_stride * b->rs.ch;
-    const size_t orow = sizeof(float) * (size_t)out_stride * b->rs.ch;
+    const size_t frame = sizeof(float) * b->rs.ch, row = frame * (size_t)sample_stride, orow = frame * (size_t)out_stride;
     /* the stage reads a block's samples after it wrote earlier blocks: not in place */
     const uintptr_t s0 = (uintptr_t)samples, o0 = (uintptr_t)out;
     if (row && orow && s0 < o0 + orow * n && o0 < s0 + row * n) return MP3D_E_ARG;
     HIPCHK(hipSetDevice(b->device));
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : b->own;
-    int r = call_begin(b, s);
-    if (r) return r;
+    RCCHK(call_begin(b, s));
     CallEnd done{b, s};
-    const float *dsmp = samples;
-    const int32_t *dcin = (const int32_t *)counts;
+    const float *dsmp;
+    const int32_t *dcin;
     bool host_in = false;
-    if (sample_stride && !is_device_ptr(samples, b->device)) {
-        r = b->sx.smp.grow(b, row * n);
-        if (r) return r;
-        HIPCHK(hipMemcpyAsync(b->sx.smp, samples, row * n, hipMemcpyDefault, s));
-        dsmp = b->sx.smp;
-        host_in = true;
-    } else if (sample_stride && (uintptr_t)samples % sizeof(float)) {
-        return MP3D_E_ARG;
-    }
-    if (!is_device_ptr(counts, b->device)) {
-        HIPCHK(hipMemcpyAsync(b->sx.cin, counts, sizeof(int32_t) * n, hipMemcpyDefault, s));
-        dcin = b->sx.cin;
-        host_in = true;
-    } else if ((uintptr_t)counts % sizeof(int32_t)) {
-        return MP3D_E_ARG;
-    }
-    r = st_run(b, dsmp, dcin, sample_stride, n, out, out_stride, out_count, flags, s);
-    if (r) return r;
+    RCCHK(stage_inputs(b, b->sx, samples, sample_stride, frame, counts, n, s, &dsmp, &dcin, &host_in));
+    RCCHK(st_run(b, dsmp, dcin, sample_stride, n, out, out_stride, out_count, flags, s));
     if (host_in) HIPCHK(hipStreamSynchronize(s)); /* the caller's host arrays are read until here */
     return MP3D_OK;
 }
@@ -169,25 +141,14 @@ extern "C" int mp3d_batch_stretch(mp3d_batch *b, const float *samples, long long
 extern "C" int mp3d_batch_decode_stretched(mp3d_batch *b, const uint8_t *frames, const uint64_t *offsets,
                                            const uint32_t *sizes, int n, int F, float *out, long long out_stride,
                                            int *out_count, int flags, mp3d_frame_info *infos, void *hip_stream) {
-    if (!b || !b->sx.on || !out || !out_count || out_stride < 0 || out_stride > 0x7fffffffLL ||
-        (flags & ~(MP3D_PACK_FLUSH | MP3D_PACK_GAPLESS)))
-        return MP3D_E_ARG;
-    if (!frames || !offsets || !sizes || n <= 0 || F <= 0) return MP3D_E_ARG;
-    if (n > b->max_streams || F > b->max_frames) return MP3D_E_CAPACITY;
-    HIPCHK(hipSetDevice(b->device));
-    /* the packed call into the handle's own samples: a stride no stream can
-     * exceed, counts on the device, so it only queues work */
-    const long long S = mp3d_packed_max_samples(b->rs.f.hz, F, 0);
-    int r = b->sx.smp.grow(b, sizeof(float) * (size_t)S * b->rs.ch * n);
-    if (r) return r;
-    r = mp3d_batch_decode_packed(b, frames, offsets, sizes, n, F, b->sx.smp, 1, S, b->sx.cin, flags, infos, hip_stream);
-    if (r) return r;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : b->own;
+    if (!b || !b->sx.on || !out || !out_count || out_stride < 0 || out_stride > 0x7fffffffLL) return MP3D_E_ARG;
+    long long S;
+    hipStream_t s;
+    RCCHK(decode_to_stage(b, b->sx, frames, offsets, sizes, n, F, flags, infos, hip_stream, &S, &s));
     CallEnd done{b, s};
     return st_run(b, b->sx.smp, b->sx.cin, S, n, out, out_stride, out_count, flags, s);
 }
 
 extern "C" int mp3d_batch_stretch_time(mp3d_batch *b, float *us) {
-    if (!b || !us || !b->timing || !b->sx.tm.timed) return MP3D_E_ARG;
-    return b->sx.tm.elapsed_us(us);
+    return b ? stage_time(b, b->sx.tm, us) : MP3D_E_ARG;
 }

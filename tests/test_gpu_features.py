@@ -320,6 +320,25 @@ def test_argument_errors(batch):
     dec.reset()
     out, counts, _ = dec.decode_packed(batch.blob, offs, sizes, batch.F, flush=True)
     assert counts.max() > 0
+    # device pointers must be int-aligned: counts and feat_count as well
+    dec = handle(2, 80, True)
+    x5 = np.ascontiguousarray((np.random.default_rng(5).standard_normal((1, 5000)) * 0.25).astype(np.float32))
+    cnt, fc = np.array([5000], np.int32), np.zeros(1, np.int32)
+    feat = np.zeros((1, 40, 80), np.float32)
+    dcnt = torch.tensor([0, 5000, 0, 0], dtype=torch.int32, device="cuda")
+    dfc = torch.zeros(4, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+
+    def call(cp=cnt.ctypes.data, fcp=fc.ctypes.data):
+        return L.mp3d_batch_features(dec._h, x5.ctypes.data, 5000, cp, 1, feat.ctypes.data, 40, fcp, mp3_amd.PACK_FLUSH,
+                                     None)
+
+    assert call(cp=dcnt.data_ptr() + 1) == -1 and call(cp=dcnt.data_ptr() + 2) == -1
+    assert call(fcp=dfc.data_ptr() + 2) == -1
+    assert call() == 0 and fc[0] == ceil_frames(5000)
+    assert call(cp=dcnt.data_ptr() + 4, fcp=dfc.data_ptr() + 4) == 0
+    dec.sync()
+    assert dfc.cpu().tolist() == [0, int(fc[0]), 0, 0]
 
 
 def test_off_and_on_again(batch, decoded):

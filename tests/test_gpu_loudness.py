@@ -408,6 +408,34 @@ def test_argument_errors(batch):
     assert call(0, bp=dblk.data_ptr() + 1) == -1
     assert call(0) == 0 and bc[0] == 1 and pk[0] == np.abs(x).max()
     assert call(mp3_amd.PACK_FLUSH, sp=dsmp.data_ptr() + 4, bp=dblk.data_ptr() + 4) == 0 and bc[0] == 1
+    # device pointers must be int-aligned: counts and block_count as well
+    dcnt = torch.tensor([0, 5000, 0, 0], dtype=torch.int32, device="cuda")
+    dbc = torch.zeros(4, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+
+    def call_counts(cp=cnt.ctypes.data, bcp=bc.ctypes.data):
+        return L.mp3d_batch_loudness(dec._h, smp.ctypes.data, 5000, cp, 1, blocks.ctypes.data, 4, bcp, pk.ctypes.data,
+                                     mp3_amd.PACK_FLUSH, None)
+
+    assert call_counts(cp=dcnt.data_ptr() + 1) == -1 and call_counts(cp=dcnt.data_ptr() + 2) == -1
+    assert call_counts(bcp=dbc.data_ptr() + 2) == -1
+    bc[0] = -7
+    assert call_counts() == 0 and bc[0] == 1
+    assert call_counts(cp=dcnt.data_ptr() + 4, bcp=dbc.data_ptr() + 4) == 0
+    dec.sync()
+    assert dbc.cpu().tolist() == [0, 1, 0, 0]
+    lufs = np.zeros(1, np.float32)
+
+    def integrated(cp):
+        lufs[0] = 5.0
+        return L.mp3d_batch_loudness_integrated(dec._h, blocks.ctypes.data, 4, cp, 1, lufs.ctypes.data, None)
+
+    assert integrated(dcnt.data_ptr() + 1) == -1 and integrated(dcnt.data_ptr() + 2) == -1
+    dcnt[1] = 1
+    torch.cuda.synchronize()
+    assert integrated(bc.ctypes.data) == 0
+    want = lufs.copy()
+    assert want[0] != 5.0 and integrated(dcnt.data_ptr() + 4) == 0 and same_bits(lufs, want)
     assert L.mp3d_batch_decode_loudness(dec._h, batch.blob.ctypes.data, offs.ctypes.data, sizes.ctypes.data, 2, 1,
                                         blocks.ctypes.data, 4, bc.ctypes.data, None, 4, None, None) == -1
     with pytest.raises(mp3_amd.MP3DError, match="-5"):

@@ -441,6 +441,13 @@ def test_argument_errors(batch):
     assert call(0, tpp=dtp.data_ptr() + 1) == -1
     assert call(0) == 0 and tp[0] >= np.abs(x[0, :4994]).max()
     assert call(mp3_amd.PACK_FLUSH, sp=dsmp.data_ptr() + 4, tpp=dtp.data_ptr() + 4) == 0
+    # device pointers must be int-aligned: counts as well
+    dcnt = torch.tensor([0, 5000, 0, 0], dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    assert call(0, cp=dcnt.data_ptr() + 1) == -1 and call(0, cp=dcnt.data_ptr() + 2) == -1
+    assert call(mp3_amd.PACK_FLUSH) == 0
+    want, tp[0] = tp[0], 0.0
+    assert want > 0.0 and call(mp3_amd.PACK_FLUSH, cp=dcnt.data_ptr() + 4) == 0 and tp[0] == want
     blocks, bc = np.zeros((2, 4), np.float32), np.zeros(2, np.int32)
 
     def measure(flags, tpp=tp.ctypes.data, n=2, F=1):
