@@ -828,8 +828,6 @@ __device__ __forceinline__ void synth_stream(const FrameRec *__restrict__ rec, c
                  * of a line with itself, then one FMA: bit-exact), but the 36
                  * VALU per granule cost more than the LDS round trip saved
                  * (A/B FQ: C3 +2 % k_synth) */
-                fusedq = PAR && var[0] == 0 && var[1] == 0 && !is_on && !ms_fold;
-                const bool longq = all_long(); /* = long / long, !is_on, !fusedq: M/S only */
                 const float rsq2 = 0.70710678118654752f;
                 /* per-band scale 2^(q/4), lane = band idx (long b | 22 + 3 b + w);
                  * the lane's scalefactor byte comes from the prefetched meta
@@ -842,6 +840,20 @@ __device__ __forceinline__ void synth_stream(const FrameRec *__restrict__ rec, c
                  * held in a VGPR across the loop) */
                 const float msf = __int_as_float(__builtin_amdgcn_readfirstlane(ms_fold ? 0x3f3504f3 : 0x3f800000));
                 auto p2q = [&](int q) { return ldexpf(T.p2q[q & 3], q >> 2) * msf; };
+                /* a requantised line below FFmpeg's fixed-point resolution is
+                 * zero: its requantiser rounds |xr| < 0.5 * 1.759 * 2^-28 to 0
+                 * (oracle ORC_FFMPEG_FLUSH, pinned by the probe_flush_*
+                 * fixtures), and the intensity boundary below sees it as zero.
+                 * |is|^(4/3) >= 1, so no line of a band whose scale 2^(q/4)
+                 * reaches the threshold 0.8795 * 2^-28 falls below it: that is
+                 * q >= -112 (2^-28 against 2^-28.25 at -113; the roundings of
+                 * the scale are far inside that step).  qmin is the lane's
+                 * smallest q, and only a granule with a band at or under
+                 * Q_FLUSH (about one in a hundred of the generator's; quiet
+                 * content) compares its lines, on the general path. */
+                constexpr int Q_FLUSH = -113;
+                const float flush = 0.5f * 1.759f / 268435456.0f * msf;
+                int qmin;
                 if (var[0] == 0 && (nch == 1 || var[1] == 0)) {
                     /* long blocks in every coded channel (the common case): both
                      * channels' 22 band scales in one pass, lane = (ch, band) */
@@ -851,12 +863,14 @@ __device__ __forceinline__ void synth_stream(const FrameRec *__restrict__ rec, c
                     const uint32_t wd = (uint32_t)__shfl((int)wm[cs], c * MW + (j >> 2));
                     const int sf = (int)(wd >> (8 * (j & 3))) & 0xFF;
                     const int pre = (g11 & 0xFFu) ? (int)(MP3D_PRETAB_BITS >> (2 * j)) & 3 : 0;
-                    const float v = p2q(gain - ((sf + pre) << shift));
+                    qmin = gain - ((sf + pre) << shift);
+                    const float v = p2q(qmin);
                     if (bl < 22) Wd.scale[c][bl] = v;
+                    if (!(bl < 22 && c < nch)) qmin = 0;
                 } else {
                     const bool lng = lane < 22;
                     const int b = (lane - 22) / 3, w = lane - 22 - 3 * b;
-                    auto band_scale = [&](uint32_t g10, uint32_t g11, int cbase) {
+                    auto band_q = [&](uint32_t g10, uint32_t g11, int cbase) {
                         const int gain = (int)(g10 & 0xFFu) - 210, shift = (int)(g10 >> 24) + 1;
                         const bool mixed = ((g10 >> 16) & 0xFFu) != 0u, preflag = (g11 & 0xFFu) != 0u;
                         int j = mixed ? 8 + 3 * (b - 3) + w : 3 * b + w;
@@ -865,11 +879,19 @@ __device__ __forceinline__ void synth_stream(const FrameRec *__restrict__ rec, c
                         const int sf = (int)(wd >> (8 * (j & 3))) & 0xFF;
                         const int pre = preflag ? (int)(MP3D_PRETAB_BITS >> (2 * (lane & 31))) & 3 : 0;
                         const int sbg = (int)(g11 >> (8 * (1 + (w < 3 ? w : 0)))) & 0xFF;
-                        return p2q(lng ? gain - ((sf + pre) << shift) : gain - 8 * sbg - (sf << shift));
+                        return lng ? gain - ((sf + pre) << shift) : gain - 8 * sbg - (sf << shift);
                     };
-                    Wd.scale[0][lane] = band_scale(m10a, m11a, 0);
-                    if (nch == 2) Wd.scale[1][lane] = band_scale(m10b, m11b, MW);
+                    qmin = band_q(m10a, m11a, 0);
+                    Wd.scale[0][lane] = p2q(qmin);
+                    if (nch == 2) {
+                        const int q1 = band_q(m10b, m11b, MW);
+                        Wd.scale[1][lane] = p2q(q1);
+                        qmin = q1 < qmin ? q1 : qmin;
+                    }
                 }
+                const bool qflush = __ballot(qmin <= Q_FLUSH) != 0ull; /* uniform, rare */
+                fusedq = PAR && var[0] == 0 && var[1] == 0 && !is_on && !ms_fold && !qflush;
+                const bool longq = all_long() && !qflush; /* = long / long, !is_on, !fusedq: M/S only */
                 wave_sync();
                 (void)m12a;
                 (void)m12b;
@@ -1074,6 +1096,15 @@ __device__ __forceinline__ void synth_stream(const FrameRec *__restrict__ rec, c
                         }
                     }
                 }
+                if (qflush) {
+#pragma unroll
+                    for (int i = 0; i < 5; i++)
+#pragma unroll
+                        for (int c = 0; c < 2; c++)
+#pragma unroll
+                            for (int e = 0; e < 2; e++)
+                                if (fabsf(XV(c, 2 * i + e)) < flush) XV(c, 2 * i + e) = 0.f;
+                }
                 if (is_on) {
                     /* joint stereo with MPEG-1 intensity (ISO 2.4.3.4), paired by
                      * bitstream line; the right channel's block structure and
@@ -1082,16 +1113,13 @@ __device__ __forceinline__ void synth_stream(const FrameRec *__restrict__ rec, c
                      * nzR bit = right-channel band idx holding a nonzero line. */
                     /* no intensity for is_pos >= 7 (MPEG-1), >= 16 (LSF, FFmpeg) */
                     constexpr int IS_ILLEGAL = LSF ? 16 : 7;
-                    /* a line counts as nonzero from FFmpeg's fixed-point
-                     * resolution up: its requantiser rounds |xr| below
-                     * 0.5 * 1.759 * 2^-28 to 0 (oracle ORC_FFMPEG_FLUSH,
-                     * pinned by the probe_flush_* fixtures) */
-                    constexpr float FLUSH = 0.5f * 1.759f / 268435456.0f;
+                    /* a line counts as nonzero from the flush threshold up
+                     * (msf = 1 here: intensity frames do not fold 1 / sqrt2) */
                     uint64_t nzR = 0;
 #pragma unroll
                     for (int i = 0; i < 5; i++) {
                         const uint32_t tv2 = (i < 4 || lane < 32) ? lpair[var[1]][lane + 64 * i] : 0u;
-                        if (fmaxf(fabsf(XV(1, 2 * i)), fabsf(XV(1, 2 * i + 1))) >= FLUSH)
+                        if (fmaxf(fabsf(XV(1, 2 * i)), fabsf(XV(1, 2 * i + 1))) >= flush)
                             nzR |= 1ull << ((tv2 >> 2) & 63u);
                     }
 #pragma unroll

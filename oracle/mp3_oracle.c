@@ -18,7 +18,10 @@
  * file is an independent high-precision restatement, not a bit-copy of the
  * GPU path.  Built with -DORC_REAL=float (liboracle_f32.so, -O3) the same
  * source is the single-precision CPU decoder that bench.py times as the CPU
- * baseline; the tests check only the double build.
+ * baseline.  The tests hold the GPU path to the double
+ * build alone; the float build also serves tests/test_precision_host.py as
+ * the yardstick of what plain float32 arithmetic reaches against the double
+ * build (the float sink's bound is 4 x that, tests/_precision.py).
  */
 #include <math.h>
 #include <stdint.h>

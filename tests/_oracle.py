@@ -14,19 +14,23 @@ class Info(ctypes.Structure):
                 ("layer", ctypes.c_int), ("bitrate_kbps", ctypes.c_int)]
 
 
-_lib = None
+_libs = {}
 
 
-def lib():
-    global _lib
-    if _lib is None:
-        if not LIB.exists():
-            subprocess.check_call(["make", "-s", "-C", str(ROOT / "oracle")])
-        L = ctypes.CDLL(str(LIB))
+def lib(name="liboracle.so"):
+    """The double build, or by name the float32 build (liboracle_f32.so: the
+    same source with orc_real = float)."""
+    if name not in _libs:
+        path = ROOT / "oracle" / name
+        if not path.exists():
+            subprocess.check_call(["make", "-s", "-C", str(ROOT / "oracle"), name])
+        L = ctypes.CDLL(str(path))
         L.orc_create.restype = ctypes.c_void_p
         L.orc_destroy.argtypes = [ctypes.c_void_p]
         L.orc_decode_frame.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_void_p,
                                        ctypes.POINTER(Info)]
+        L.orc_decode_frame_f64.argtypes = L.orc_decode_frame.argtypes
+        L.orc_parse_header.argtypes = [ctypes.c_char_p, ctypes.c_void_p]
         L.orc_get_taps.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 4
         L.orc_decode_stream.argtypes = [ctypes.c_char_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_long,
                                         ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
@@ -44,8 +48,8 @@ def lib():
         L.orc_skip_id3v2.argtypes = [ctypes.c_char_p, ctypes.c_long]
         L.orc_skip_id3v2.restype = ctypes.c_long
         L.orc_parse_info_tag.argtypes = [ctypes.c_char_p, ctypes.c_long, ctypes.c_void_p]
-        _lib = L
-    return _lib
+        _libs[name] = L
+    return _libs[name]
 
 
 def info_tag(data: bytes):
@@ -76,8 +80,8 @@ def decode_stream(data: bytes, max_frames=100000, opts=0):
 class Decoder:
     """Per-frame oracle decoder with parity taps."""
 
-    def __init__(self, opts=0):
-        self.L = lib()
+    def __init__(self, opts=0, lib_name="liboracle.so"):
+        self.L = lib(lib_name)
         self.d = self.L.orc_create()
         self.L.orc_set_options(self.d, int(opts))
 
@@ -91,6 +95,14 @@ class Decoder:
         pcm = np.zeros((2, 1152), np.float32)
         info = Info()
         r = self.L.orc_decode_frame(self.d, frame, len(frame), pcm.ctypes.data, ctypes.byref(info))
+        return r, pcm[: info.channels], info
+
+    def decode_frame_f64(self, frame: bytes):
+        """The frame's samples as the build computed them, unrounded: float64
+        [channels, 1152] (576 used for an LSF frame)"""
+        pcm = np.zeros((2, 1152), np.float64)
+        info = Info()
+        r = self.L.orc_decode_frame_f64(self.d, frame, len(frame), pcm.ctypes.data, ctypes.byref(info))
         return r, pcm[: info.channels], info
 
     def taps(self):
