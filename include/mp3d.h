@@ -969,6 +969,133 @@ MP3D_API int mp3d_batch_decode_limited(mp3d_batch *b, const uint8_t *frames, con
  * (mp3d_batch_limit, mp3d_batch_decode_limited); needs mp3d_batch_set_timing */
 MP3D_API int mp3d_batch_limiter_time(mp3d_batch *b, float *us);
 
+/* ---- segment sink (speech and pause boundaries) ----------------------------- *
+ * Where a sentence starts and ends: the sample ranges in which a stream's
+ * short-time energy stays over a threshold, pauses shorter than a minimum
+ * filled and runs shorter than a minimum dropped.
+ *
+ * Input signal of a slot: packed-sink output in the handle's format (any of
+ * the nine rates fs, C = out_channels 1 or 2, float32 interleaved):
+ * x_c[0 .. N) since the slot's last segment restart.  Sample windows and
+ * MP3D_PACK_GAPLESS act before it.  Samples are finite; a NaN gives an
+ * unspecified result but no fault.
+ *
+ * Constants: H = (fs + 50) / 100 in integer division (a hop of 10 ms, the
+ * tempo sink's H: 441 at 44.1 kHz, 221 at 22 050 Hz, 110 at 11 025 Hz).  Per
+ * handle, in hops: the pause P and the shortest segment S, both in [1, 256],
+ * and pad with 0 <= 2 pad <= P.  Per slot: the threshold thr, an unsigned
+ * 64-bit hop energy with 1 <= thr <= H * 2^30.
+ *
+ * Hop energy, integers after one float32 quantisation:
+ *   m[i] = x_0[i] (mono), 0.5f * (x_0[i] + x_1[i]) (stereo), float32, the tempo
+ *          sink's mix
+ *   q[i] = (int) clamp(floor(m[i] * 32768 + 0.5), -32768, 32767), the packed
+ *          sink's int16 rule: the product and the sum are exact, never rounded
+ *   E[b] = sum_{n < H} q[bH + n]^2, q outside [0, N) = 0      (uint64: up to H * 2^30)
+ *   a[b] = E[b] >= thr
+ * B is the number of hops known: floor(N / H) before a flush, ceil(N / H) at a
+ * flush (the open hop is completed with zeros).  a outside [0, B) is 0.
+ *
+ * Masks:
+ *   c[b] = 1 iff there are i <= b <= j with a[i] = a[j] = 1 and j - i <= P
+ *   o[b] = 1 iff there is t with t <= b <= t + S - 1 and c[t .. t + S - 1] all 1
+ * In this order: a pause of fewer than P hops between two active hops is
+ * filled (leading and trailing silence never is), then a run of fewer than S
+ * hops is dropped.  So a run of o is at least S hops long, and two runs are at
+ * least P hops apart.
+ *
+ * Segments: each maximal run [b0, b1) of o is one segment,
+ *   start = max(b0 - pad, 0) * H,  end = min((b1 + pad) * H, N)
+ * both long long, in samples since the slot's restart.  With 2 pad <= P padded
+ * segments never overlap.
+ *
+ * Emit rule: o[b] depends on a[b - S + 1 - P .. b + S - 1 + P] and on nothing
+ * else, so it is final once b <= B - S - P.  A segment is emitted by the call
+ * after which b1 <= B - S - P, that is, once sample (b1 + S + P) H - 1 has been
+ * seen.  MP3D_PACK_FLUSH emits every remaining segment, an open one closed at
+ * b1 = B with end = N; then the slot restarts.  The min with N acts at a flush
+ * only, so any split of a stream into calls emits the same list.
+ *
+ * Bound: the end edges b1 a call decides lie in a range of at most K + S + P
+ * hop indices, K = ceil((in_samples + H - 1) / H) being the most hops the call
+ * can complete, the pending part hop included: (B0 - S - P, B1 - S - P] with
+ * B1 - B0 <= K without a flush, (B0 - S - P, B1] with one.  Two end edges are
+ * at least S + P apart (a run, then a gap).  So a call emits at most
+ * 1 + (K + S + P - 1) / (S + P) <= mp3d_segment_max = 2 + K / (S + P) segments,
+ * in integer division.
+ *
+ * Overflow: a slot whose call would emit more than seg_stride segments gets
+ * count -1, writes nothing and restarts.
+ *
+ * The per-slot segment state (N, the open hop's partial energy, an integer and
+ * so exact under any split, the last 1024 = 2 (S + P) bits of a at P = S = 256,
+ * and the last rising edge of o: 152 bytes) lives in the handle while the sink
+ * is set, not in the state blob.  It restarts where the limiter's does: at
+ * create, at mp3d_batch_reset, at mp3d_batch_set_state on its slot, at
+ * mp3d_batch_set_output (which also turns the sink off), at
+ * mp3d_batch_set_segments, at mp3d_batch_set_window on its slot, after its own
+ * flush and after an overflow; and at mp3d_batch_set_segment_threshold on its
+ * slots.  The threshold outlives a restart, as the tempo does.               */
+
+/* host only: the hop energy of a mean square of db dBFS at rate hz,
+ * max(1, ceil(H * 2^30 * 10^(db / 10))) computed in double, -96 <= db <= 0;
+ * MP3D_E_ARG for another db or a rate that is not an MPEG audio rate */
+MP3D_API long long mp3d_segment_threshold(int hz, double db);
+
+/* host only: a seg_stride no slot can exceed in one call that feeds in_samples
+ * (at most 2^31 - 1) samples, whatever earlier calls left pending and flushed
+ * or not: 2 + K / (speech_hops + pause_hops), K = ceil((in_samples + H - 1) / H).
+ * MP3D_E_ARG for a bad rate, count or number of hops. */
+MP3D_API long long mp3d_segment_max(int hz, long long in_samples, int pause_hops, int speech_hops);
+
+/* Needs a packed format (mp3d_batch_set_output), pause_hops and speech_hops in
+ * [1, 256] and 0 <= 2 pad_hops <= pause_hops, else MP3D_E_ARG.  on != 0 sets
+ * P, S and pad, every slot's threshold to mp3d_segment_threshold(fs, -40.0),
+ * restarts every slot's segment state and waits for the handle's work; on = 0
+ * turns the sink off and frees its buffers. */
+MP3D_API int mp3d_batch_set_segments(mp3d_batch *b, int on, int pause_hops, int speech_hops, int pad_hops);
+
+/* The threshold of slots [first, first + n): thr is a host array.  Restarts
+ * those slots' segment state and waits for the handle's work.  MP3D_E_ARG
+ * (nothing written) for a threshold outside [1, H * 2^30] or before
+ * mp3d_batch_set_segments; MP3D_E_CAPACITY past max_streams. */
+MP3D_API int mp3d_batch_set_segment_threshold(mp3d_batch *b, int first, int n, const unsigned long long *thr);
+
+/* The stage: feeds counts[s] (clamped to [0, sample_stride]) sample frames
+ * from samples + s * sample_stride * out_channels per stream through the
+ * slots' segment state and writes the segments the call emits as (start, end)
+ * pairs to seg + s * seg_stride * 2 and their number to seg_count[s] (-1: over
+ * seg_stride).  Nothing past seg_count[s] pairs is written.  samples, counts,
+ * seg and seg_count are host or device memory (a host samples array is read
+ * whole; a host seg is filled by one copy per stream); the call is
+ * asynchronous when all four are device memory.  Device pointers must be
+ * element-aligned (a device seg to 8 bytes), else MP3D_E_ARG; sample_stride is
+ * at most 2^31 - 1 - 960 and seg_stride at most 2^31 - 1, and n_streams *
+ * ceil(K / 64) at most (2^32 - 1) / 256, the launch's size, else
+ * MP3D_E_CAPACITY.  flags: MP3D_PACK_FLUSH only.  Runs on the device out and
+ * out_count of mp3d_batch_decode_packed (float32), of mp3d_batch_stretch or of
+ * mp3d_batch_limit, or with n_streams = 1 on the device output of
+ * mp3d_batch_decode_long_packed: the energy tiles are independent, so one long
+ * stream is spread over the whole GPU.  Leaves decoder, resampler and every
+ * other sink's state untouched.  MP3D_E_ARG before mp3d_batch_set_segments.  */
+MP3D_API int mp3d_batch_segments(mp3d_batch *b, const float *samples, long long sample_stride, const int *counts,
+                                 int n_streams, long long *seg, long long seg_stride, int *seg_count, int flags,
+                                 void *hip_stream);
+
+/* mp3d_batch_decode_packed (float32) into a handle-owned buffer of stride
+ * mp3d_packed_max_samples(out_hz, frames_per_stream, 0) with device counts,
+ * then the stage on them.  flags: MP3D_PACK_FLUSH | MP3D_PACK_GAPLESS, both
+ * forwarded (the flush ends the resampler, then the segments).              */
+MP3D_API int mp3d_batch_decode_segments(mp3d_batch *b, const uint8_t *frames, const uint64_t *offsets,
+                                        const uint32_t *sizes, int n_streams, int frames_per_stream, long long *seg,
+                                        long long seg_stride, int *seg_count, int flags, mp3d_frame_info *infos,
+                                        void *hip_stream);
+
+/* device-side microseconds of the segment stage of the last segment call
+ * (mp3d_batch_segments, mp3d_batch_decode_segments); needs
+ * mp3d_batch_set_timing */
+MP3D_API int mp3d_batch_segment_time(mp3d_batch *b, float *us);
+
 /* ---- diagnostics -------------------------------------------------------- */
 MP3D_API const char *mp3d_strerror(int err);
 MP3D_API int mp3d_last_hip_error(void);

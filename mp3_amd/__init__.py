@@ -64,7 +64,9 @@ EXPORTS = ["mp3d_dec_create", "mp3d_dec_create_on", "mp3d_dec_destroy", "mp3d_de
            "mp3d_stretch_max_samples", "mp3d_batch_set_stretch", "mp3d_batch_set_tempo", "mp3d_batch_stretch",
            "mp3d_batch_decode_stretched", "mp3d_batch_stretch_time", "mp3d_limiter_lookahead",
            "mp3d_limiter_max_samples", "mp3d_batch_set_limiter", "mp3d_batch_limit", "mp3d_batch_decode_limited",
-           "mp3d_batch_limiter_time"]
+           "mp3d_batch_limiter_time", "mp3d_segment_threshold", "mp3d_segment_max", "mp3d_batch_set_segments",
+           "mp3d_batch_set_segment_threshold", "mp3d_batch_segments", "mp3d_batch_decode_segments",
+           "mp3d_batch_segment_time"]
 
 OPT_CRC_CHECK = 1  # MP3D_OPT_CRC_CHECK: drop frames whose CRC-16 mismatches
 LONG_GAPLESS = 1  # MP3D_LONG_GAPLESS: apply the LAME tag's trim inside decode_long_packed
@@ -184,6 +186,16 @@ def _bind(L):
         L.mp3d_batch_decode_limited.argtypes = [vp, vp, u64p, u32p, i, i, vp, vp, i, ctypes.c_longlong, vp, vp, i, vp,
                                                 vp]
         L.mp3d_batch_limiter_time.argtypes = [vp, vp]
+    if hasattr(L, "mp3d_batch_set_segments"):  # (an older build loaded for an A/B lacks the segment sink)
+        L.mp3d_segment_threshold.argtypes = [i, ctypes.c_double]
+        L.mp3d_segment_threshold.restype = ctypes.c_longlong
+        L.mp3d_segment_max.argtypes = [i, ctypes.c_longlong, i, i]
+        L.mp3d_segment_max.restype = ctypes.c_longlong
+        L.mp3d_batch_set_segments.argtypes = [vp, i, i, i, i]
+        L.mp3d_batch_set_segment_threshold.argtypes = [vp, i, i, vp]
+        L.mp3d_batch_segments.argtypes = [vp, vp, ctypes.c_longlong, vp, i, vp, ctypes.c_longlong, vp, i, vp]
+        L.mp3d_batch_decode_segments.argtypes = [vp, vp, u64p, u32p, i, i, vp, ctypes.c_longlong, vp, i, vp, vp]
+        L.mp3d_batch_segment_time.argtypes = [vp, vp]
     if hasattr(L, "mp3d_debug_wglds_probe"):  # libmp3d_wglds.so only (tests/test_gpu_wglds.py)
         L.mp3d_debug_wglds_probe.argtypes = [i, i, vp, i]
     return L
@@ -421,6 +433,7 @@ class BatchDecoder:
         self._tp = False  # and the true-peak tap
         self._stretch = False  # and the tempo sink
         self._limit = None  # and the limiter (its ceiling in dBTP while it is on)
+        self._segments = None  # and the segment sink (its pause and shortest segment in hops while it is on)
 
     def decode_packed(self, frames, offsets, sizes, frames_per_stream, out=None, counts=None, infos=None, f32=True,
                       flush=False, stride=None, stream=None, gapless=False):
@@ -913,6 +926,115 @@ class BatchDecoder:
         call (after set_timing)."""
         return self._stage_us(self._L.mp3d_batch_limiter_time)
 
+    def set_segments(self, on=True, threshold_db=-40.0, min_pause_ms=300, min_speech_ms=100, pad_ms=50):
+        """Turn the segment sink on or off (mp3d_batch_set_segments): the
+        sample ranges of the packed output, whatever its format, in which the
+        energy of 10 ms hops stays at or over threshold_db dBFS (-96 .. 0),
+        pauses shorter than min_pause_ms filled, then runs shorter than
+        min_speech_ms dropped, each range widened by pad_ms (at most half the
+        pause).  The times become hops by round(ms / 10); the defaults are
+        conventions, not measurements.  Needs set_output.  Restarts every
+        stream's segment state."""
+        hops = [int(round(ms / 10.0)) for ms in (min_pause_ms, min_speech_ms, pad_ms)]
+        self._ck(self._L.mp3d_batch_set_segments(self._h, int(bool(on)), *hops))
+        self._segments = (hops[0], hops[1]) if on else None
+        if on and float(threshold_db) != -40.0:
+            self.set_segment_threshold(db=threshold_db, n=self.max_streams)
+
+    def set_segment_threshold(self, db=None, energy=None, first=0, n=1):
+        """The threshold of streams first, first + 1 ...
+        (mp3d_batch_set_segment_threshold): energy, hop energies in
+        [1, H * 2^30] (a scalar or a sequence, one per stream), or db, one
+        level in dBFS for n streams (segment_threshold).  Restarts those
+        streams' segment state."""
+        if (db is None) == (energy is None):
+            raise ValueError("one of db and energy")
+        if energy is None:
+            energy = [segment_threshold(getattr(self, "_out", (0, 0))[0], db)] * int(n)
+        thr = np.ascontiguousarray(energy, np.uint64).reshape(-1)
+        self._ck(self._L.mp3d_batch_set_segment_threshold(self._h, int(first), thr.size, thr.ctypes.data))
+
+    def _segment_args(self, n, seg, seg_counts, stride, default_stride):
+        hz, ch = getattr(self, "_out", (0, 0))
+        if stride is None:  # (sink off: the call fails with MP3D_E_ARG)
+            on = getattr(self, "_segments", None)
+            stride = int(seg.shape[1]) if seg is not None else default_stride(hz, *on) if on else 1
+        stride = int(stride)
+        if seg is None:
+            seg = np.zeros((n, stride, 2), np.int64)
+        if seg_counts is None:
+            seg_counts = np.zeros(n, np.int32)
+        return seg, seg_counts, stride
+
+    def segments(self, samples, counts, seg=None, seg_counts=None, flush=False, stride=None, stream=None):
+        """The segment sink alone (mp3d_batch_segments): samples float32
+        [n, sample_stride, channels] in the packed format, counts int32 [n]
+        sample frames per stream (both host arrays or device tensors), e.g.
+        the device out and counts of decode_packed, stretch or limit.  seg:
+        None (allocate host) or int64 array/tensor [n, stride, 2]; seg_counts
+        int32 [n].  stride defaults to seg's, else to the bound that cannot
+        overflow.  flush=True emits the rest of every stream, an open segment
+        closed at its end, and restarts it.  Returns (seg, seg_counts): stream
+        s holds seg_counts[s] pairs (start, end) in samples since its restart
+        (-1: over the stride)."""
+        n, ss = int(samples.shape[0]), int(samples.shape[1])
+        if not hasattr(counts, "data_ptr"):
+            counts = np.ascontiguousarray(counts, np.int32)
+        seg, seg_counts, stride = self._segment_args(n, seg, seg_counts, stride,
+                                                     lambda hz, p, sp: segment_max(hz, ss, p, sp))
+        sp, k1 = _ptr(samples)
+        cp, k2 = _ptr(counts)
+        gp, k3 = _ptr(seg)
+        gc, k4 = _ptr(seg_counts)
+        self._ck(self._L.mp3d_batch_segments(self._h, sp if ss else None, ss, cp, n, gp, stride, gc, _pack_flags(flush),
+                                             _stream(stream)))
+        return seg, seg_counts
+
+    def decode_segments(self, frames, offsets, sizes, frames_per_stream, seg=None, counts=None, infos=None,
+                        flush=False, stride=None, stream=None, gapless=False):
+        """Decode as decode_packed does (float32) and write every stream's
+        segments (mp3d_batch_decode_segments).  stride defaults to seg's, else
+        to the bound that cannot overflow.  flush and gapless as in
+        decode_packed; the flush also ends the segments.  Returns (seg, counts,
+        infos)."""
+        off, sz = self._geom(offsets, sizes)
+        n, F = off.size, int(frames_per_stream)
+        seg, counts, stride = self._segment_args(
+            n, seg, counts, stride, lambda hz, p, sp: segment_max(hz, packed_max_samples(hz, F), p, sp))
+        if infos is None:
+            infos = np.zeros((n, F), FRAME_INFO_DT)
+        fp, k1 = _ptr(frames)
+        gp, k2 = _ptr(seg)
+        cp, k3 = _ptr(counts)
+        ip, k4 = _ptr(infos)
+        self._ck(self._L.mp3d_batch_decode_segments(self._h, fp, off.ctypes.data, sz.ctypes.data, n, F, gp, stride, cp,
+                                                    _pack_flags(flush, gapless), ip, _stream(stream)))
+        return seg, counts, infos
+
+    def segment_time_us(self):
+        """Device-side microseconds of the segment stage of the last segment
+        call (after set_timing)."""
+        return self._stage_us(self._L.mp3d_batch_segment_time)
+
+    def long_segments(self, data, segment_frames=32, gapless=True):
+        """The sentences of one file: decode_long_packed at the handle's
+        format into a tensor on the handle's device, then segments(flush=True)
+        on it as one stream.  Needs set_segments.  Returns (int64 [k, 2] of
+        (start, end) in samples, the pcm tensor [n, channels], StreamInfo,
+        in_hz)."""
+        import torch
+
+        hz, ch = getattr(self, "_out", (0, 0))
+        if getattr(self, "_segments", None) is None:
+            raise MP3DError("long_segments needs set_segments")
+        host = data.cpu().numpy().tobytes() if hasattr(data, "cpu") else bytes(data)
+        cap = max(1, long_packed_bound(host, hz))
+        out = torch.zeros((cap, ch), dtype=torch.float32, device="cuda:%d" % self.device)
+        pcm, si, in_hz = self.decode_long_packed(data, hz, ch, segment_frames, out=out, gapless=gapless)
+        n = int(pcm.shape[0])
+        seg, cnt = self.segments(out[None, : max(n, 1)], [n], flush=True)
+        return seg[0, : int(cnt[0])].copy(), pcm, si, in_hz
+
     def decode_normalized(self, frames, offsets, sizes, frames_per_stream, target=-23.0, max_dbtp=-1.0, out=None,
                           f32=True, gapless=False, limit=False):
         """Decode streams that are whole in this call and normalise them to
@@ -1188,6 +1310,18 @@ def limiter_max_samples(hz, in_samples):
     """Smallest stride of limit that can never overflow for one call feeding
     in_samples samples (mp3d_limiter_max_samples): in_samples + A + 6."""
     return int(_check(lib().mp3d_limiter_max_samples(int(hz), int(in_samples))))
+
+
+def segment_threshold(hz, db):
+    """The segment sink's threshold for a mean square of db dBFS (-96 .. 0) at
+    rate hz, as a hop energy (mp3d_segment_threshold; no GPU needed)."""
+    return int(_check(lib().mp3d_segment_threshold(int(hz), float(db))))
+
+
+def segment_max(hz, in_samples, pause_hops, speech_hops):
+    """Smallest stride of segments that can never overflow for one call
+    feeding in_samples samples (mp3d_segment_max)."""
+    return int(_check(lib().mp3d_segment_max(int(hz), int(in_samples), int(pause_hops), int(speech_hops))))
 
 
 def long_packed_bound(data, out_hz):

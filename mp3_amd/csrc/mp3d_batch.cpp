@@ -131,7 +131,7 @@ extern "C" int mp3d_batch_create(int device, int max_streams, int max_frames, mp
         return MP3D_E_HIP;
     }
     for (auto &e : b->ev) (void)hipEventCreate(&e);
-    for (StageTimer *t : {&b->rs.tm, &b->ft.tm, &b->ld.tm, &b->nm.tm, &b->sx.tm, &b->lm.tm})
+    for (StageTimer *t : {&b->rs.tm, &b->ft.tm, &b->ld.tm, &b->nm.tm, &b->sx.tm, &b->lm.tm, &b->sg.tm})
         for (auto &e : t->ev) (void)hipEventCreate(&e);
     r = b->st_mem.grow(b, sizeof(StreamState) * ns);
     if (!r) r = b->rec.grow(b, sizeof(FrameRec) * fr);
@@ -179,7 +179,7 @@ extern "C" void mp3d_batch_destroy(mp3d_batch *b) {
     }
     for (hipEvent_t e : b->ev)
         if (e) (void)hipEventDestroy(e);
-    for (StageTimer *t : {&b->rs.tm, &b->ft.tm, &b->ld.tm, &b->nm.tm, &b->sx.tm, &b->lm.tm})
+    for (StageTimer *t : {&b->rs.tm, &b->ft.tm, &b->ld.tm, &b->nm.tm, &b->sx.tm, &b->lm.tm, &b->sg.tm})
         for (hipEvent_t e : t->ev)
             if (e) (void)hipEventDestroy(e);
     if (b->ev_done) (void)hipEventDestroy(b->ev_done);

@@ -1,7 +1,8 @@
 /*
  * mp3d_host.h -- private to the host sources (mp3d_host_tables.cpp,
  * mp3d_batch.cpp, mp3d_long.cpp, mp3d_dec.cpp, mp3d_sinks.cpp,
- * mp3d_loudness.cpp, mp3d_normalize.cpp, mp3d_stretch.cpp, mp3d_limiter.cpp):
+ * mp3d_loudness.cpp, mp3d_normalize.cpp, mp3d_stretch.cpp, mp3d_limiter.cpp,
+ * mp3d_segment.cpp):
  * the error macros, the owning device buffer, the batch handle, the frame
  * that the calls of the stages behind the packed sink share, and the internal
  * functions that cross those files.  Nothing here is exported (the library
@@ -30,6 +31,7 @@
 #include "mp3d_normalize.h"
 #include "mp3d_stretch.h"
 #include "mp3d_limiter.h"
+#include "mp3d_segment.h"
 #include "mp3d_launch.h"
 
 namespace mp3d {
@@ -315,6 +317,21 @@ struct mp3d_batch {
             on = false, A = 0, c = 1.0f;
         }
     } lm;
+    /* segment sink (mp3d_batch_set_segments; mp3d_segment.h): on = false is
+     * off, and then none of its buffers exists.  st, plan, thr (it outlives a
+     * restart of st) and part hold max_streams entries; the per-tile activity
+     * words bits grow with the calls. */
+    struct SegmentSink : Stage {
+        bool on = false;
+        int H = 0, P = 0, S = 0, pad = 0; /* the hop in samples; pause, shortest segment and pad in hops */
+        mp3d::DevBuf<SgState> st;
+        mp3d::DevBuf<SgPlan> plan;
+        mp3d::DevBuf<uint64_t> thr, part, bits;
+        void off() {
+            Stage::off(), st.release(), plan.release(), thr.release(), part.release(), bits.release();
+            on = false, H = P = S = pad = 0;
+        }
+    } sg;
 };
 
 namespace mp3d {
@@ -375,7 +392,9 @@ inline bool is_device_ptr(const void *p, int device) { return ptr_kind(p, device
  * over the timers in mp3d_batch.cpp (create, destroy); nothing else names
  * them all. */
 /* they read the packed sink's format: off with any change of it */
-inline void stages_off(mp3d_batch *b) { b->ft.off(), b->ld.off(), b->nm.off(), b->ga.off(), b->sx.off(), b->lm.off(); }
+inline void stages_off(mp3d_batch *b) {
+    b->ft.off(), b->ld.off(), b->nm.off(), b->ga.off(), b->sx.off(), b->lm.off(), b->sg.off();
+}
 template <class S> hipError_t stage_restart(const DevBuf<S> &st, int first, int n, hipStream_t s) {
     return st ? hipMemsetAsync(st + first, 0, sizeof(S) * (size_t)n, s) : hipSuccess;
 }
@@ -386,6 +405,7 @@ inline int stages_restart(mp3d_batch *b, int first, int n, hipStream_t s) {
     HIPCHK(stage_restart(b->nm.st, first, n, s));
     HIPCHK(stage_restart(b->sx.st, first, n, s));
     HIPCHK(stage_restart(b->lm.st, first, n, s));
+    HIPCHK(stage_restart(b->sg.st, first, n, s));
     return MP3D_OK;
 }
 

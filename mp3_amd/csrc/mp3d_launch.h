@@ -11,7 +11,7 @@
 #include <stdint.h>
 
 /* (layouts: mp3d_internal.h, mp3d_resample.h, mp3d_features.h, mp3d_loudness.h, mp3d_normalize.h,
- * mp3d_stretch.h, mp3d_limiter.h) */
+ * mp3d_stretch.h, mp3d_limiter.h, mp3d_segment.h) */
 struct StreamState; struct FrameRec; struct UnitMeta; struct DevTables;
 struct RsState; struct RsCfg; struct RsPlan; struct RsLong;
 struct FtState; struct FtPlan; struct FtTab;
@@ -19,6 +19,7 @@ struct LdState; struct LdPlan; struct LdTab;
 struct TpState; struct TpPlan;
 struct StState; struct StPlan;
 struct LimState; struct LimPlan;
+struct SgState; struct SgPlan;
 
 namespace mp3d {
 
@@ -124,6 +125,14 @@ void launch_limiter(const float *samples, const int32_t *counts, LimState *st, L
                     const float *gain, void *out, int32_t *out_count, float *tilemin, float *gr, bool f32, int ch, int n,
                     long long sample_stride, long long out_stride, int tiles, int A, float c, int flush,
                     hipStream_t strm);
+
+/* ---- mp3d_segment.hip ---- */
+/* k_sg_plan + k_sg_energy + k_sg_emit: packed float32 samples to the sample ranges of their speech segments; part
+ * holds n words, bits n * tiles (a word per tile of MP3D_SG_TILE hops), seg n * seg_stride pairs */
+void launch_segments(const float *samples, const int32_t *counts, SgState *st, SgPlan *plan, const uint64_t *thr,
+                     uint64_t *part, uint64_t *bits, long long *seg, int32_t *seg_count, int ch, int n,
+                     long long sample_stride, long long seg_stride, int tiles, int H, int P, int S, int pad, int flush,
+                     hipStream_t strm);
 
 } // namespace mp3d
 
