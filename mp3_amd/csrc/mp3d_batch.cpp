@@ -18,10 +18,7 @@ hipError_t mp3d::state_clear(StreamState *st, int n, hipStream_t s) {
     return e;
 }
 
-static bool poison_env() {
-    const char *e = getenv("MP3D_DEBUG_POISON");
-    return e && e[0] && strcmp(e, "0") != 0;
-}
+static bool poison_env() { return env_flag("MP3D_DEBUG_POISON"); }
 
 /* Frames per k_synth segment for n streams x F frames: few streams leave
  * the chip idle (one wave walks one stream), so each stream is split into
@@ -38,9 +35,8 @@ static int seg_frames(int n, int F, int n_cu, int min_len) {
         const int nseg = (int)std::min<long long>((want + n - 1) / n, F / min_len);
         seg_len = (F + nseg - 1) / nseg;
     }
-    const char *e = getenv("MP3D_SEG_FRAMES");
-    if (e && atoi(e) > 0) seg_len = std::min(F, atoi(e));
-    if (e && atoi(e) == 0 && e[0] == '0') seg_len = F;
+    const int v = env_int("MP3D_SEG_FRAMES", -1, -1, F);
+    if (v > 0 || (v == 0 && env_is("MP3D_SEG_FRAMES", "0"))) seg_len = v ? v : F;
     return seg_len;
 }
 
@@ -72,10 +68,7 @@ int mp3d::flush_tail(mp3d_batch *b, hipStream_t s) {
 }
 
 static int tail_plan(mp3d_batch *b, int n, int F, int seg_len, hipStream_t s, TailPlan *tp) {
-    if (b->tail_live >= 0 && (seg_len >= F || b->tail_n != n)) {
-        int r = flush_tail(b, s);
-        if (r) return r;
-    }
+    if (b->tail_live >= 0 && (seg_len >= F || b->tail_n != n)) RCCHK(flush_tail(b, s));
     tp->in = b->tail_live >= 0 ? b->st_tail[b->tail_live].p : nullptr;
     tp->t_out = b->tail_live >= 0 ? b->tail_live ^ 1 : 0;
     tp->out = nullptr;
@@ -83,8 +76,7 @@ static int tail_plan(mp3d_batch *b, int n, int F, int seg_len, hipStream_t s, Ta
         DevBuf<float> &t = b->st_tail[tp->t_out];
         const size_t need = STATE_TAIL * (size_t)n;
         const bool fresh = need > t.cap;
-        int r = t.grow(b, need);
-        if (r) return r;
+        RCCHK(t.grow(b, need));
         /* k_synth writes the fifo slots the synthesis reads back (slot 0 only
          * at the columns some lane's window needs): zero the rest once, as
          * StreamState is, so a flushed tail leaves the same state bytes */
@@ -109,8 +101,7 @@ PtrKind mp3d::ptr_kind(const void *p, int device) {
 extern "C" int mp3d_batch_create(int device, int max_streams, int max_frames, mp3d_batch **out) {
     if (!out || max_streams <= 0 || max_frames <= 0) return MP3D_E_ARG;
     *out = nullptr;
-    int r = device_init(device);
-    if (r) return r;
+    RCCHK(device_init(device));
     mp3d_batch *b = new (std::nothrow) mp3d_batch;
     if (!b) return MP3D_E_NOMEM;
     b->device = device;
@@ -121,28 +112,23 @@ extern "C" int mp3d_batch_create(int device, int max_streams, int max_frames, mp
     const size_t ns = (size_t)max_streams, fr = ns * max_frames, units = fr * 4;
     bool ok = hipStreamCreateWithFlags(&b->own, hipStreamNonBlocking) == hipSuccess &&
               hipStreamCreateWithFlags(&b->copy, hipStreamNonBlocking) == hipSuccess &&
-              hipEventCreateWithFlags(&b->ev_done, hipEventDisableTiming) == hipSuccess;
+              b->ev_done.create(hipEventDisableTiming) == hipSuccess;
     for (auto &g : b->geo)
-        ok = ok && hipHostMalloc((void **)&g.h, 20 * ns) == hipSuccess &&
-             hipEventCreateWithFlags(&g.staged, hipEventDisableTiming) == hipSuccess &&
-             hipEventCreateWithFlags(&g.freed, hipEventDisableTiming) == hipSuccess;
+        ok = ok && g.h.alloc(20 * ns, hipHostMallocDefault, b->poison) == hipSuccess &&
+             g.staged.create(hipEventDisableTiming) == hipSuccess &&
+             g.freed.create(hipEventDisableTiming) == hipSuccess;
     if (!ok) {
         mp3d_batch_destroy(b);
         return MP3D_E_HIP;
     }
-    for (auto &e : b->ev) (void)hipEventCreate(&e);
-    for (StageTimer *t : {&b->rs.tm, &b->ft.tm, &b->ld.tm, &b->nm.tm, &b->sx.tm, &b->lm.tm, &b->sg.tm})
-        for (auto &e : t->ev) (void)hipEventCreate(&e);
-    r = b->st_mem.grow(b, sizeof(StreamState) * ns);
+    int r = b->st_mem.grow(b, sizeof(StreamState) * ns);
     if (!r) r = b->rec.grow(b, sizeof(FrameRec) * fr);
     if (!r) r = b->sideu.grow(b, sizeof(uint64_t) * units);
     if (!r) r = b->is_buf.grow(b, sizeof(int16_t) * MP3D_IS_ROW * units);
     if (!r) r = b->meta.grow(b, sizeof(UnitMeta) * units);
     if (!r) r = b->rank.grow(b, sizeof(uint32_t) * units);
-    for (auto &g : b->geo) {
+    for (auto &g : b->geo)
         if (!r) r = g.d.grow(b, 20 * ns);
-        poison_host(b->poison, g.h, 20 * ns);
-    }
     if (!r) r = b->d_infos.grow(b, sizeof(mp3d_frame_info) * fr);
     if (!r) r = b->d_work.grow(b, 256);
     if (r) {
@@ -150,7 +136,7 @@ extern "C" int mp3d_batch_create(int device, int max_streams, int max_frames, mp
         return r;
     }
     b->st = b->st_mem;
-    if (getenv("MP3D_DEBUG_ADDR")) /* placement diagnostics (tools/dbg/place.py) */
+    if (env_set("MP3D_DEBUG_ADDR")) /* placement diagnostics (tools/dbg/place.py) */
         fprintf(stderr, "mp3d: st %p rec %p sideu %p is_buf %p meta %p infos %p\n", (void *)b->st, (void *)b->rec,
                 (void *)b->sideu, (void *)b->is_buf, (void *)b->meta, (void *)b->d_infos);
     /* zeroed on the handle's own stream and waited for: a null-stream
@@ -172,27 +158,15 @@ extern "C" void mp3d_batch_destroy(mp3d_batch *b) {
     if (b->ev_done) (void)hipEventSynchronize(b->ev_done);
     if (b->own) (void)hipStreamSynchronize(b->own);
     if (b->copy) (void)hipStreamSynchronize(b->copy);
-    for (auto &g : b->geo) {
-        if (g.h) (void)hipHostFree(g.h);
-        if (g.staged) (void)hipEventDestroy(g.staged);
-        if (g.freed) (void)hipEventDestroy(g.freed);
-    }
-    for (hipEvent_t e : b->ev)
-        if (e) (void)hipEventDestroy(e);
-    for (StageTimer *t : {&b->rs.tm, &b->ft.tm, &b->ld.tm, &b->nm.tm, &b->sx.tm, &b->lm.tm, &b->sg.tm})
-        for (hipEvent_t e : t->ev)
-            if (e) (void)hipEventDestroy(e);
-    if (b->ev_done) (void)hipEventDestroy(b->ev_done);
     if (b->own) (void)hipStreamDestroy(b->own);
     if (b->copy) (void)hipStreamDestroy(b->copy);
-    delete b; /* frees every device buffer, after the waits above */
+    delete b; /* frees every device and pinned buffer and every event, after the waits above */
 }
 
 extern "C" int mp3d_batch_reset(mp3d_batch *b) {
     if (!b) return MP3D_E_ARG;
     HIPCHK(hipSetDevice(b->device));
-    int r = own_after_last(b);
-    if (r) return r;
+    RCCHK(own_after_last(b));
     b->tail_live = -1; /* the state is zeroed whole */
     HIPCHK(state_clear(b->st, b->max_streams, b->own));
     if (b->rs.st) HIPCHK(hipMemsetAsync(b->rs.st, 0, sizeof(RsState) * (size_t)b->max_streams, b->own));
@@ -239,27 +213,18 @@ extern "C" int mp3d_batch_kernel_times(mp3d_batch *b, float *us3) {
 #define MP3D_WIDE_STREAMS 256
 /* MP3D_DEMUX=lane | wave forces the demux path (tests run both) */
 static bool demux_wide(int n) {
-    const char *e = getenv("MP3D_DEMUX");
-    if (e && !strcmp(e, "lane")) return true;
-    if (e && !strcmp(e, "wave")) return false;
-    return n >= MP3D_WIDE_STREAMS;
+    return env_is("MP3D_DEMUX", "lane") || (n >= MP3D_WIDE_STREAMS && !env_is("MP3D_DEMUX", "wave"));
 }
 
 /* MP3D_SYNTH_LONGPATH=0 sends every granule through k_synth's general phase
  * Q and alias step (tests compare the two paths bit for bit); default on */
-static bool synth_longpath() {
-    const char *e = getenv("MP3D_SYNTH_LONGPATH");
-    return !(e && !strcmp(e, "0"));
-}
+static bool synth_longpath() { return !env_is("MP3D_SYNTH_LONGPATH", "0"); }
 
 /* batches of at most this many units (frame granule channels) decode one
  * unit per wave (k_huffman_wave); MP3D_HUFF=wave | lane forces the kernel */
 #define MP3D_WAVE_HUFF_UNITS 1024
 static bool huffman_wave(int n_units) {
-    const char *e = getenv("MP3D_HUFF");
-    if (e && !strcmp(e, "wave")) return true;
-    if (e && !strcmp(e, "lane")) return false;
-    return n_units <= MP3D_WAVE_HUFF_UNITS;
+    return env_is("MP3D_HUFF", "wave") || (n_units <= MP3D_WAVE_HUFF_UNITS && !env_is("MP3D_HUFF", "lane"));
 }
 
 /* a call compares the new geometry with the current slot's and skips the
@@ -300,8 +265,7 @@ int mp3d::prepare_geometry(mp3d_batch *b, const uint64_t *offsets, const uint32_
     memcpy(g.h + 2 * (size_t)n, sizes, sizeof(uint32_t) * n);
     /* growing md frees the old region: hipFree waits for the device */
     const size_t md_was = b->md.cap;
-    int r = b->md.grow(b, o + 8192);
-    if (r) return r;
+    RCCHK(b->md.grow(b, o + 8192));
     /* a new region starts zeroed: the Huffman staging reads whole words up
      * to 2 past a unit's end, and a corrupt unit may decode past its
      * payload -- those bits then read as zeros (FFmpeg's buffer padding),
@@ -316,79 +280,80 @@ int mp3d::prepare_geometry(mp3d_batch *b, const uint64_t *offsets, const uint32_
     return MP3D_OK;
 }
 
+/* The front half's kernels on stream s between events 0 and 2 of the timing
+ * chain: `demux` (the caller's launch of k_demux / k_walk or k_demux_fp, for
+ * call_seq as counted here), then k_huffman over the md region it filled,
+ * the streams' offsets in it at md_off.  wide: the demux is k_walk. */
+template <class D>
+static int front_kernels(mp3d_batch *b, bool wide, D &&demux, const uint64_t *md_off, int n, int F, bool huff_wave,
+                         uint32_t *rank, hipStream_t s) {
+    DeviceCtx &dc = g_dev[b->device];
+    RCCHK(core_mark(b, 0, s));
+    if (++b->call_seq == 0) b->call_seq = 1; /* (d_work[1] starts at 0) */
+    b->fam_ok = wide;
+    RCCHK(core_launch(b, 1, s, demux));
+    return core_launch(b, 2, s, [&] {
+        launch_huffman(b->md, md_off, b->rec, b->sideu, dc.tables, b->is_buf, b->meta, n, F, dc.n_cu, huff_wave,
+                       b->d_work, rank, s);
+    });
+}
+
 /* Front half shared by decode and huffman_only: input staging, k_demux,
- * k_huffman. */
-/* mapped: frames (and dev_infos) are host memory the device reads / writes
- * directly (the per-frame decoder's pinned buffers): no staging copies */
-static int run_front(mp3d_batch *b, const uint8_t *frames, const uint64_t *offsets, const uint32_t *sizes, int n,
-                     int F, hipStream_t s, bool *sync_needed, bool mapped = false,
-                     mp3d_frame_info *dev_infos = nullptr) {
-    if (!b || !frames || !offsets || !sizes || n <= 0 || F <= 0) return MP3D_E_ARG;
+ * k_huffman; the frame infos go to dinf (device-accessible).  c.mapped: the
+ * frames need no staging copy. */
+static int run_front(mp3d_batch *b, const DecodeCall &c, mp3d_frame_info *dinf, hipStream_t s, bool *sync_needed) {
+    const int n = c.n, F = c.F;
+    if (!c.frames || !c.offsets || !c.sizes || n <= 0 || F <= 0) return MP3D_E_ARG;
     if (n > b->max_streams || F > b->max_frames) return MP3D_E_CAPACITY;
-    int r = call_begin(b, s); /* (the demux and Huffman stages never touch a live tail's overlap / fifo) */
-    if (r) return r;
+    RCCHK(call_begin(b, s)); /* (the demux and Huffman stages never touch a live tail's overlap / fifo) */
     uint64_t total = 0;
-    for (int i = 0; i < n; i++) total = std::max<uint64_t>(total, offsets[i] + sizes[i]);
-    const uint8_t *din = frames;
-    if (!mapped && !is_device_ptr(frames, b->device)) {
-        r = b->d_in.grow(b, total + 64);
-        if (r) return r;
-        HIPCHK(hipMemcpyAsync(b->d_in, frames, total, hipMemcpyDefault, s));
+    for (int i = 0; i < n; i++) total = std::max<uint64_t>(total, c.offsets[i] + c.sizes[i]);
+    const uint8_t *din = c.frames;
+    if (!c.mapped && !is_device_ptr(c.frames, b->device)) {
+        RCCHK(b->d_in.grow(b, total + 64));
+        HIPCHK(hipMemcpyAsync(b->d_in, c.frames, total, hipMemcpyDefault, s));
         din = b->d_in;
         *sync_needed = true;
     }
-    r = prepare_geometry(b, offsets, sizes, n, s);
-    if (r) return r;
-    const mp3d_batch::Geo &g = b->geo[b->geo_i];
-    DeviceCtx &dc = g_dev[b->device];
-    if (b->timing) HIPCHK(hipEventRecord(b->ev[0], s));
+    RCCHK(prepare_geometry(b, c.offsets, c.sizes, n, s));
+    mp3d_batch::Geo &g = b->geo[b->geo_i];
     /* demux + main-data gather: lane-per-stream walk + payload copy for wide
      * batches, one wave per stream below MP3D_WIDE_STREAMS (fewer launches) */
     const bool wide = demux_wide(n);
-    if (++b->call_seq == 0) b->call_seq = 1; /* (d_work[1] starts at 0) */
-    b->fam_ok = wide;
-    if (b->poison) launch_lds_poison(dc.n_cu, s);
-    launch_demux(din, g.in_off(), g.in_len(), b->md, g.md_off(), b->st, b->rec, b->sideu,
-                 dev_infos ? (void *)dev_infos : b->d_infos.p, n, F, b->opts, wide, b->d_work + 1, b->call_seq, s);
-    if (b->timing) HIPCHK(hipEventRecord(b->ev[1], s));
-    if (b->poison) launch_lds_poison(dc.n_cu, s);
-    launch_huffman(b->md, g.md_off(), b->rec, b->sideu, dc.tables, b->is_buf, b->meta, n, F, dc.n_cu,
-                   huffman_wave(n * F * 4), b->d_work, b->rank, s);
+    RCCHK(front_kernels(
+        b, wide,
+        [&] {
+            launch_demux(din, g.in_off(), g.in_len(), b->md, g.md_off(), b->st, b->rec, b->sideu, dinf, n, F, b->opts,
+                         wide, b->d_work + 1, b->call_seq, s);
+        },
+        g.md_off(), n, F, huffman_wave(n * F * 4), b->rank, s));
     HIPCHK(hipEventRecord(g.freed, s)); /* the slot's last reader */
-    b->geo[b->geo_i].fresh = true;
-    if (b->timing) HIPCHK(hipEventRecord(b->ev[2], s));
-    HIPCHK(hipGetLastError());
+    g.fresh = true;
     return MP3D_OK;
 }
 
 /* the front half for one run of pre-located frames (FpRun, mp3d_host.h) */
-static int run_front_fp(mp3d_batch *b, const FpRun &fp, int F, hipStream_t s, mp3d_frame_info *dev_infos) {
+static int run_front_fp(mp3d_batch *b, const FpRun &fp, int F, mp3d_frame_info *dinf, hipStream_t s) {
     if (b->max_streams != 1 || F <= 0 || F > 64 || F > b->max_frames) return MP3D_E_ARG;
-    int r = call_begin(b, s);
-    if (r) return r;
+    RCCHK(call_begin(b, s));
     if (b->md.cap < (size_t)fp.len + MP3D_RES_BYTES + 8192) return MP3D_E_CAPACITY; /* sized at create */
-    DeviceCtx &dc = g_dev[b->device];
-    if (b->timing) HIPCHK(hipEventRecord(b->ev[0], s));
-    if (++b->call_seq == 0) b->call_seq = 1;
-    b->fam_ok = false;
-    if (b->poison) launch_lds_poison(dc.n_cu, s);
-    launch_demux_fp(fp.in, fp.len, fp.fo, b->md, b->st, fp.tail_in, fp.snap, b->rec, b->sideu,
-                    dev_infos ? (void *)dev_infos : b->d_infos.p, F, b->opts, s);
-    if (b->timing) HIPCHK(hipEventRecord(b->ev[1], s));
     /* md offset of the one stream: a zero word of d_work (d_work[4..5]) */
-    if (b->poison) launch_lds_poison(dc.n_cu, s);
-    launch_huffman(b->md, (const uint64_t *)(b->d_work + 4), b->rec, b->sideu, dc.tables, b->is_buf, b->meta, 1, F,
-                   dc.n_cu, true, b->d_work, nullptr, s);
-    if (b->timing) HIPCHK(hipEventRecord(b->ev[2], s));
-    HIPCHK(hipGetLastError());
-    return MP3D_OK;
+    return front_kernels(
+        b, false,
+        [&] {
+            launch_demux_fp(fp.in, fp.len, fp.fo, b->md, b->st, fp.tail_in, fp.snap, b->rec, b->sideu, dinf, F,
+                            b->opts, s);
+        },
+        (const uint64_t *)(b->d_work + 4), 1, F, true, nullptr, s);
 }
 
-int mp3d::batch_decode(mp3d_batch *b, const uint8_t *frames, const uint64_t *offsets, const uint32_t *sizes, int n,
-                       int F, void *pcm, bool f32, mp3d_frame_info *infos, void *hip_stream, bool overwrite, int kinds,
-                       bool mapped, int seg_len_req, const FpRun *fp, bool async) {
-    if (!b || !pcm) return MP3D_E_ARG;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : b->own;
+int mp3d::batch_decode(mp3d_batch *b, const DecodeCall &c) {
+    if (!b || !c.pcm || (c.async && !c.mapped)) return MP3D_E_ARG;
+    const int n = c.n, F = c.F;
+    void *const pcm = c.pcm;
+    mp3d_frame_info *const infos = c.infos;
+    const bool f32 = c.f32, mapped = c.mapped;
+    hipStream_t s = c.hip_stream ? (hipStream_t)c.hip_stream : b->own;
     CallEnd done{b, s};
     bool sync_needed = mapped;
     /* frame infos: written in place when the caller's array is device memory
@@ -396,17 +361,14 @@ int mp3d::batch_decode(mp3d_batch *b, const uint8_t *frames, const uint64_t *off
      * copied to the host after the call */
     const bool inf_host = infos && !mapped && !is_device_ptr(infos, b->device); /* or another GPU's */
     mp3d_frame_info *dinf = infos && !inf_host ? infos : b->d_infos.p;
-    int r = fp ? run_front_fp(b, *fp, F, s, dinf) : run_front(b, frames, offsets, sizes, n, F, s, &sync_needed, mapped, dinf);
-    if (r) return r;
-    if (async && !mapped) return MP3D_E_ARG;
+    RCCHK(c.fp ? run_front_fp(b, *c.fp, F, dinf, s) : run_front(b, c, dinf, s, &sync_needed));
     const size_t PB = f32 ? sizeof(float) : sizeof(int16_t), row = 2304 * PB;
     const size_t pcm_bytes = (size_t)n * F * row;
     void *dpcm = pcm;
     const PtrKind pk = mapped ? PTR_DEV : ptr_kind(pcm, b->device);
     bool pcm_host = pk == PTR_HOST;
     if (pk != PTR_DEV) {
-        r = b->d_pcm.grow(b, pcm_bytes);
-        if (r) return r;
+        RCCHK(b->d_pcm.grow(b, pcm_bytes));
         dpcm = b->d_pcm;
         /* another GPU's buffer: its rows the kernel does not write keep their
          * bytes, as in place (copied over, decoded into, copied back) */
@@ -415,18 +377,16 @@ int mp3d::batch_decode(mp3d_batch *b, const uint8_t *frames, const uint64_t *off
     DeviceCtx &dc = g_dev[b->device];
     /* few streams: frame-parallel segments per stream (>= 4 frames each,
      * or the caller's seg_len) */
-    const int seg_len = seg_len_req > 0 ? std::min(F, seg_len_req) : seg_frames(n, F, dc.n_cu, 4);
+    const int seg_len = c.seg_len > 0 ? std::min(F, c.seg_len) : seg_frames(n, F, dc.n_cu, 4);
     TailPlan tp;
-    r = tail_plan(b, n, F, seg_len, s, &tp);
-    if (r) return r;
-    if (b->poison) launch_lds_poison(dc.n_cu, s);
-    launch_synth(b->rec, b->is_buf, b->meta, dc.tables, b->st, dpcm, f32, n, F, kinds, seg_len, tp.out, tp.in,
-                 b->fam_ok ? b->d_work + 1 : nullptr, b->call_seq, dc.n_cu, synth_longpath(), s);
-    if (b->timing) HIPCHK(hipEventRecord(b->ev[3], s));
-    HIPCHK(hipGetLastError());
+    RCCHK(tail_plan(b, n, F, seg_len, s, &tp));
+    RCCHK(core_launch(b, 3, s, [&] {
+        launch_synth(b->rec, b->is_buf, b->meta, dc.tables, b->st, dpcm, f32, n, F, c.kinds, seg_len, tp.out, tp.in,
+                     b->fam_ok ? b->d_work + 1 : nullptr, b->call_seq, dc.n_cu, synth_longpath(), s);
+    }));
     tail_commit(b, n, F, seg_len, tp);
     const size_t ib = sizeof(mp3d_frame_info) * (size_t)n * F;
-    if (pcm_host && !overwrite) {
+    if (pcm_host && !c.clobber_unwritten) {
         /* A host sink is read back whole, but each row keeps the caller's
          * bytes the kernel did not write (rows without audio, the second
          * half of a mono / LSF row): those few spans are saved from the
@@ -466,19 +426,28 @@ int mp3d::batch_decode(mp3d_batch *b, const uint8_t *frames, const uint64_t *off
         HIPCHK(hipMemcpyAsync(infos, b->d_infos, ib, hipMemcpyDefault, s));
         sync_needed = sync_needed || ptr_kind(infos, b->device) == PTR_HOST;
     }
-    if (sync_needed && !async) HIPCHK(hipStreamSynchronize(s));
+    if (sync_needed && !c.async) HIPCHK(hipStreamSynchronize(s));
     return MP3D_OK;
+}
+
+/* the public decodes: the call as the ABI states it, the options at their defaults */
+static int decode_public(mp3d_batch *b, const uint8_t *frames, const uint64_t *offsets, const uint32_t *sizes, int n,
+                         int F, void *pcm, bool f32, mp3d_frame_info *infos, void *hip_stream) {
+    DecodeCall c;
+    c.frames = frames, c.offsets = offsets, c.sizes = sizes, c.n = n, c.F = F;
+    c.pcm = pcm, c.f32 = f32, c.infos = infos, c.hip_stream = hip_stream;
+    return batch_decode(b, c);
 }
 
 extern "C" int mp3d_batch_decode(mp3d_batch *b, const uint8_t *frames, const uint64_t *offsets, const uint32_t *sizes,
                                  int n, int F, int16_t *pcm, mp3d_frame_info *infos, void *hip_stream) {
-    return batch_decode(b, frames, offsets, sizes, n, F, pcm, false, infos, hip_stream, false);
+    return decode_public(b, frames, offsets, sizes, n, F, pcm, false, infos, hip_stream);
 }
 
 extern "C" int mp3d_batch_decode_f32(mp3d_batch *b, const uint8_t *frames, const uint64_t *offsets,
                                      const uint32_t *sizes, int n, int F, float *pcm, mp3d_frame_info *infos,
                                      void *hip_stream) {
-    return batch_decode(b, frames, offsets, sizes, n, F, pcm, true, infos, hip_stream, false);
+    return decode_public(b, frames, offsets, sizes, n, F, pcm, true, infos, hip_stream);
 }
 
 extern "C" int mp3d_batch_huffman_only(mp3d_batch *b, const uint8_t *frames, const uint64_t *offsets,
@@ -492,12 +461,12 @@ extern "C" int mp3d_batch_huffman_only(mp3d_batch *b, const uint8_t *frames, con
     if (n > 0 && F > 0 && n <= b->max_streams && F <= b->max_frames) {
         /* k_huffman stores only each row's nonzero prefix (nz_end); the tap
          * returns whole rows, so clear them first */
-        int r = call_begin(b, s);
-        if (r) return r;
+        RCCHK(call_begin(b, s));
         HIPCHK(hipMemsetAsync(b->is_buf, 0, units * MP3D_IS_ROW * sizeof(int16_t), s));
     }
-    int r = run_front(b, frames, offsets, sizes, n, F, s, &sync_needed);
-    if (r) return r;
+    DecodeCall c; /* (its input only: the tap has no sink) */
+    c.frames = frames, c.offsets = offsets, c.sizes = sizes, c.n = n, c.F = F;
+    RCCHK(run_front(b, c, b->d_infos, s, &sync_needed));
     if (is_out) {
         HIPCHK(hipMemcpy2DAsync(is_out, 576 * sizeof(int16_t), b->is_buf, MP3D_IS_ROW * sizeof(int16_t),
                                 576 * sizeof(int16_t), units, hipMemcpyDefault, s));
@@ -518,10 +487,7 @@ extern "C" int mp3d_batch_synth_only(mp3d_batch *b, const float *xr, const uint8
     int sr = hz == 44100 ? 0 : hz == 48000 ? 1 : hz == 32000 ? 2 : -1;
     if (sr < 0) return MP3D_E_ARG;
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : b->own;
-    {
-        int r = call_begin(b, s);
-        if (r) return r;
-    }
+    RCCHK(call_begin(b, s));
     CallEnd done{b, s};
     bool sync_needed = false;
     size_t nx = (size_t)n * F * 2 * nch;
@@ -529,8 +495,7 @@ extern "C" int mp3d_batch_synth_only(mp3d_batch *b, const float *xr, const uint8
     const uint8_t *dbt = block_type, *dmx = mixed;
     if (!is_device_ptr(xr, b->device) || !is_device_ptr(block_type, b->device) || !is_device_ptr(mixed, b->device)) {
         size_t need = nx * 576 * sizeof(float) + 2 * nx + 64;
-        int r = b->d_xr.grow(b, need);
-        if (r) return r;
+        RCCHK(b->d_xr.grow(b, need));
         uint8_t *base = b->d_xr;
         HIPCHK(hipMemcpyAsync(base, xr, nx * 576 * sizeof(float), hipMemcpyDefault, s));
         HIPCHK(hipMemcpyAsync(base + nx * 576 * sizeof(float), block_type, nx, hipMemcpyDefault, s));
@@ -545,28 +510,21 @@ extern "C" int mp3d_batch_synth_only(mp3d_batch *b, const float *xr, const uint8
     const PtrKind pk = ptr_kind(pcm, b->device);
     const bool pcm_host = pk != PTR_DEV; /* host, or another GPU's (staged like host) */
     if (pcm_host) {
-        int r = b->d_pcm.grow(b, pcm_bytes);
-        if (r) return r;
+        RCCHK(b->d_pcm.grow(b, pcm_bytes));
         dpcm = b->d_pcm;
         /* mono rows are half written: the rest keeps the caller's bytes */
         if (pk == PTR_OTHER_DEV || nch == 1) HIPCHK(hipMemcpyAsync(dpcm, pcm, pcm_bytes, hipMemcpyDefault, s));
     }
     DeviceCtx &dc = g_dev[b->device];
-    if (b->timing) {
-        for (int i = 0; i < 3; i++) HIPCHK(hipEventRecord(b->ev[i], s));
-    }
+    for (int i = 0; i < 3; i++) RCCHK(core_mark(b, i, s)); /* no front half: its events back to back */
     /* few streams: frame-parallel segments (seg_frames; one warm-up frame
      * each, so >= 4 frames per segment: warm-up overhead <= 25 %) */
     const int seg_len = seg_frames(n, F, dc.n_cu, 4);
     TailPlan tp;
-    {
-        int r = tail_plan(b, n, F, seg_len, s, &tp);
-        if (r) return r;
-    }
-    if (b->poison) launch_lds_poison(dc.n_cu, s);
-    launch_synth_xr(dxr, dbt, dmx, dc.tables, b->st, dpcm, n, F, nch, sr, seg_len, tp.out, tp.in, s);
-    if (b->timing) HIPCHK(hipEventRecord(b->ev[3], s));
-    HIPCHK(hipGetLastError());
+    RCCHK(tail_plan(b, n, F, seg_len, s, &tp));
+    RCCHK(core_launch(b, 3, s, [&] {
+        launch_synth_xr(dxr, dbt, dmx, dc.tables, b->st, dpcm, n, F, nch, sr, seg_len, tp.out, tp.in, s);
+    }));
     tail_commit(b, n, F, seg_len, tp);
     if (pcm_host) {
         HIPCHK(hipMemcpyAsync(pcm, dpcm, pcm_bytes, hipMemcpyDefault, s));
@@ -596,8 +554,7 @@ extern "C" int mp3d_batch_stream_info(mp3d_batch *b, int n, mp3d_stream_info *ou
     HIPCHK(hipSetDevice(b->device));
     /* StreamState tag_info, tag_frames, kind: three consecutive words */
     std::vector<uint32_t> tag((size_t)n * 3);
-    int r = own_after_last(b); /* after the handle's last call, on any stream */
-    if (r) return r;
+    RCCHK(own_after_last(b)); /* after the handle's last call, on any stream */
     HIPCHK(hipMemcpy2DAsync(tag.data(), 3 * sizeof(uint32_t), &b->st[0].tag_info, sizeof(StreamState),
                             3 * sizeof(uint32_t), n, hipMemcpyDeviceToHost, b->own));
     HIPCHK(hipStreamSynchronize(b->own));
@@ -621,8 +578,7 @@ int mp3d::blob_check(mp3d_batch *b, int n, const void *src) {
         for (int i = 0; i < n; i++) memcpy(&fmt[i], f0 + sizeof(StreamState) * (size_t)i, sizeof(uint32_t));
     } else {
         HIPCHK(hipSetDevice(b->device));
-        int r = own_after_last(b);
-        if (r) return r;
+        RCCHK(own_after_last(b));
         HIPCHK(hipMemcpy2DAsync(fmt.data(), sizeof(uint32_t), f0, sizeof(StreamState), sizeof(uint32_t), (size_t)n,
                                 hipMemcpyDefault, b->own));
         HIPCHK(hipStreamSynchronize(b->own));
@@ -635,16 +591,11 @@ int mp3d::blob_check(mp3d_batch *b, int n, const void *src) {
 static int state_copy(mp3d_batch *b, int first, int n, void *dst, const void *src, bool out) {
     if (!b || !(out ? dst : src) || first < 0 || n <= 0) return MP3D_E_ARG;
     if ((long long)first + n > b->max_streams) return MP3D_E_CAPACITY;
-    if (!out) {
-        const int rb = blob_check(b, n, src); /* before anything is written */
-        if (rb) return rb;
-    }
+    if (!out) RCCHK(blob_check(b, n, src)); /* before anything is written */
     HIPCHK(hipSetDevice(b->device));
     hipStream_t s = b->own;
-    int r = own_after_last(b); /* after the handle's last call, on any stream */
-    if (r) return r;
-    r = flush_tail(b, s);
-    if (r) return r;
+    RCCHK(own_after_last(b)); /* after the handle's last call, on any stream */
+    RCCHK(flush_tail(b, s));
     StreamState *at = b->st + first;
     HIPCHK(hipMemcpyAsync(out ? dst : (void *)at, out ? (const void *)at : src, sizeof(StreamState) * (size_t)n,
                           hipMemcpyDefault, s));
@@ -692,8 +643,7 @@ extern "C" __attribute__((visibility("default"))) int mp3d_debug_wglds_probe(int
     const int W = wglds_probe_words();
     if (!out_words) return W;
     if (n_groups <= 0 || n_groups > (1 << 16) || words < W) return MP3D_E_ARG;
-    int r = device_init(device);
-    if (r) return r;
+    RCCHK(device_init(device));
     uint32_t *d = nullptr;
     const size_t n = (size_t)n_groups * (W + 1);
     HIPCHK(hipMalloc(&d, n * sizeof(uint32_t)));

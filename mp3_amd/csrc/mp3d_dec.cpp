@@ -22,17 +22,15 @@ struct mp3d_dec {
     mp3d_batch *b = nullptr;
     long frames = 0;
     int kind = 0; /* MPEG family of the stream's first frame (StreamState.kind) */
-    uint8_t *h_in = nullptr;            /* pinned: the frame, zero-padded      */
-    float *h_out = nullptr;             /* pinned: one frame of PCM            */
-    mp3d_frame_info *h_info = nullptr;  /* pinned: its frame info              */
-    /* device addresses of the three (mapped): the kernels read the frame and
-     * write PCM + info in place, no copies (null: staged copies instead) */
-    uint8_t *m_in = nullptr;
-    float *m_out = nullptr;
-    mp3d_frame_info *m_info = nullptr;
+    /* pinned, with their device addresses (.m) when mapped: the kernels read
+     * the frame and write PCM + info in place, no copies (.m null: staged
+     * copies instead) */
+    PinBuf<uint8_t> in;           /* the frame, zero-padded */
+    PinBuf<float> out;            /* one frame of PCM       */
+    PinBuf<mp3d_frame_info> info; /* its frame info         */
     /* one-launch path (k_frame): the kernel writes the call's sequence
      * number into this mapped word after its PCM; the host polls it */
-    uint32_t *h_done = nullptr, *m_done = nullptr;
+    PinBuf<uint32_t> done;
     uint32_t seq = 0;
     bool fused = false;
     /* Read-ahead: the player hands over the
@@ -57,13 +55,14 @@ struct mp3d_dec {
         size_t pos;        /* bytes skipped before it in its call's buffer */
     };
     struct Run {
-        uint8_t *in = nullptr;        /* pinned, mapped: frames back to back, then the u32 frame offsets */
-        uint8_t *in_m = nullptr;      /* its device address: k_demux_fp reads it in place (all frames at
-                                       * once, so one PCIe round trip per phase, not one per frame) */
-        void *pcm = nullptr, *pcm_m = nullptr; /* [ra_max][2304] f32-sized slots (mapped) */
-        mp3d_frame_info *inf = nullptr, *inf_m = nullptr;
-        DevBuf<StreamState> snap;     /* device: the state before the run */
-        hipEvent_t done = nullptr;    /* the run's batch call has completed */
+        /* pinned, mapped.  in: frames back to back, then the u32 frame offsets;
+         * k_demux_fp reads it in place (all frames at once, so one PCIe round
+         * trip per phase, not one per frame) */
+        PinBuf<uint8_t> in;
+        PinBuf<uint8_t> pcm; /* [ra_max][2304] f32-sized slots */
+        PinBuf<mp3d_frame_info> inf;
+        DevBuf<StreamState> snap; /* device: the state before the run */
+        Event done;               /* the run's batch call has completed */
         std::vector<RaEnt> ents;
         uint32_t fo_at = 0;           /* byte offset of the frame offsets in in / dev */
         bool f32 = false;
@@ -122,17 +121,7 @@ static void dec_free(mp3d_dec *d) {
         d->wk.join(); /* (after its last job) */
     }
     if (d->b) mp3d_batch_destroy(d->b); /* (waits for the handle's work, a next run included) */
-    if (d->h_in) (void)hipHostFree(d->h_in);
-    if (d->h_out) (void)hipHostFree(d->h_out);
-    if (d->h_info) (void)hipHostFree(d->h_info);
-    if (d->h_done) (void)hipHostFree(d->h_done);
-    for (auto &u : d->run) {
-        if (u.in) (void)hipHostFree(u.in);
-        if (u.pcm) (void)hipHostFree(u.pcm);
-        if (u.inf) (void)hipHostFree(u.inf);
-        if (u.done) (void)hipEventDestroy(u.done);
-    }
-    delete d;
+    delete d;                           /* frees its pinned buffers and the runs' events */
 }
 
 static void ra_worker(mp3d_dec *d);
@@ -141,60 +130,43 @@ extern "C" int mp3d_dec_create_on(int device, mp3d_dec **out) {
     *out = nullptr;
     mp3d_dec *d = new (std::nothrow) mp3d_dec;
     if (!d) return MP3D_E_NOMEM;
-    {
-        const char *e = getenv("MP3D_PF_READAHEAD");
-        d->ra_max = e ? std::max(0, std::min(64, atoi(e))) : MP3D_PF_READAHEAD;
-        const char *g = getenv("MP3D_PF_RA_SEG");
-        if (g) d->ra_seg = std::max(1, atoi(g));
-        if (d->ra_max < 2) d->ra_max = 0;
-        const char *nx = getenv("MP3D_PF_RA_NEXT");
-        d->ra_next_on = !(nx && !strcmp(nx, "0"));
-        const char *th = getenv("MP3D_PF_RA_THREAD");
-        d->wk_on = !(th && !strcmp(th, "0"));
-        /* test hooks: the helper's launch delayed, the n-th next-run launch
-         * failed after it ran (tests/test_gpu_poison.py) */
-        const char *dl = getenv("MP3D_DEBUG_RA_DELAY_US");
-        d->wk_delay_us = dl ? std::max(0, atoi(dl)) : 0;
-        const char *fl = getenv("MP3D_DEBUG_RA_FAIL");
-        d->dbg_fail = fl ? std::max(0, atoi(fl)) : 0;
-    }
-    int r = mp3d_batch_create(device, 1, std::max(1, d->ra_max), &d->b);
-    if (r) {
+    const int imax = 0x7fffffff;
+    d->ra_max = env_int("MP3D_PF_READAHEAD", MP3D_PF_READAHEAD, 0, 64);
+    if (d->ra_max < 2) d->ra_max = 0;
+    d->ra_seg = env_int("MP3D_PF_RA_SEG", MP3D_PF_RA_SEG, 1, imax);
+    d->ra_next_on = !env_is("MP3D_PF_RA_NEXT", "0");
+    d->wk_on = !env_is("MP3D_PF_RA_THREAD", "0");
+    /* test hooks: the helper's launch delayed, the n-th next-run launch
+     * failed after it ran (tests/test_gpu_poison.py) */
+    d->wk_delay_us = env_int("MP3D_DEBUG_RA_DELAY_US", 0, 0, imax);
+    d->dbg_fail = env_int("MP3D_DEBUG_RA_FAIL", 0, 0, imax);
+    /* a failure from here on: everything made so far freed */
+    auto fail = [d](int rc) {
         dec_free(d);
-        return r;
-    }
+        return rc;
+    };
+    if (const int r = mp3d_batch_create(device, 1, std::max(1, d->ra_max), &d->b)) return fail(r);
     /* the buffers the device writes are coherent (not cached in the GPU's
-     * L2), so the completion word's fence orders them for the host */
+     * L2), so the completion word's fence orders them for the host;
+     * MP3D_DEBUG_POISON: the per-call pinned buffers too */
     const unsigned co = hipHostMallocMapped | hipHostMallocCoherent;
-    if (hipHostMalloc((void **)&d->h_in, MP3D_PF_BYTES) != hipSuccess ||
-        hipHostMalloc((void **)&d->h_out, sizeof(float) * 2304, co) != hipSuccess ||
-        hipHostMalloc((void **)&d->h_info, sizeof(mp3d_frame_info), co) != hipSuccess ||
-        hipHostMalloc((void **)&d->h_done, 64, co) != hipSuccess) {
-        dec_free(d);
-        return MP3D_E_NOMEM;
-    }
-    if (d->b->poison) { /* MP3D_DEBUG_POISON: the per-call pinned buffers too */
-        poison_host(true, d->h_in, MP3D_PF_BYTES);
-        poison_host(true, d->h_out, sizeof(float) * 2304);
-        poison_host(true, d->h_info, sizeof(mp3d_frame_info));
-    }
-    *d->h_done = 0u;
-    if (!getenv("MP3D_PF_STAGED") && hipHostGetDevicePointer((void **)&d->m_in, d->h_in, 0) == hipSuccess &&
-        hipHostGetDevicePointer((void **)&d->m_out, d->h_out, 0) == hipSuccess &&
-        hipHostGetDevicePointer((void **)&d->m_info, d->h_info, 0) == hipSuccess &&
-        hipHostGetDevicePointer((void **)&d->m_done, d->h_done, 0) == hipSuccess) {
+    const bool poison = d->b->poison;
+    if (d->in.alloc(MP3D_PF_BYTES, hipHostMallocDefault, poison) != hipSuccess ||
+        d->out.alloc(sizeof(float) * 2304, co, poison) != hipSuccess ||
+        d->info.alloc(sizeof(mp3d_frame_info), co, poison) != hipSuccess ||
+        d->done.alloc(64, co, false) != hipSuccess)
+        return fail(MP3D_E_NOMEM);
+    *d->done.p = 0u;
+    if (!env_set("MP3D_PF_STAGED") && d->in.map() == hipSuccess && d->out.map() == hipSuccess &&
+        d->info.map() == hipSuccess && d->done.map() == hipSuccess) {
         /* MP3D_PF_FUSED=0: the three-kernel path with a stream sync (tests
          * compare the two) */
-        const char *e = getenv("MP3D_PF_FUSED");
-        d->fused = !(e && !strcmp(e, "0"));
-    } else {
+        d->fused = !env_is("MP3D_PF_FUSED", "0");
+    } else { /* staged copies: no buffer counts as mapped */
         (void)hipGetLastError();
-        d->m_in = nullptr;
-        d->m_out = nullptr;
-        d->m_info = nullptr;
-        d->m_done = nullptr;
+        d->in.m = nullptr, d->out.m = nullptr, d->info.m = nullptr, d->done.m = nullptr;
     }
-    if (d->ra_max && d->m_in) {
+    if (d->ra_max && d->in.m) {
         const size_t K = (size_t)d->ra_max;
         /* the md region of a run (k_demux_fp stages no geometry): carry +
          * payloads of K maximal frames + the staging margin, zeroed */
@@ -204,30 +176,17 @@ extern "C" int mp3d_dec_create_on(int device, mp3d_dec **out) {
          * ADVICE r05) */
         if (d->b->md.grow(d->b, md_need) != MP3D_OK ||
             hipMemsetAsync(d->b->md, 0, d->b->md.cap, d->b->own) != hipSuccess ||
-            hipStreamSynchronize(d->b->own) != hipSuccess) {
-            dec_free(d);
-            return MP3D_E_NOMEM;
-        }
+            hipStreamSynchronize(d->b->own) != hipSuccess)
+            return fail(MP3D_E_NOMEM);
         /* frames, 64 zero bytes, then the frame offsets (4-B aligned) */
         const size_t in_bytes = K * MP3D_MAX_FRAME_BYTES + 64 + 4 + 4 * K;
         for (auto &u : d->run)
-            if (hipHostMalloc((void **)&u.in, in_bytes, hipHostMallocMapped) != hipSuccess ||
-                hipHostGetDevicePointer((void **)&u.in_m, u.in, 0) != hipSuccess ||
-                hipHostMalloc(&u.pcm, K * 2304 * sizeof(float), co) != hipSuccess ||
-                hipHostMalloc((void **)&u.inf, K * sizeof(mp3d_frame_info), co) != hipSuccess ||
-                u.snap.grow(d->b, sizeof(StreamState)) != MP3D_OK ||
-                hipHostGetDevicePointer(&u.pcm_m, u.pcm, 0) != hipSuccess ||
-                hipHostGetDevicePointer((void **)&u.inf_m, u.inf, 0) != hipSuccess ||
-                hipEventCreateWithFlags(&u.done, hipEventDisableTiming) != hipSuccess) {
-                dec_free(d);
-                return MP3D_E_NOMEM;
-            }
-        if (d->b->poison) /* (the runs' buffers; MP3D_DEBUG_POISON) */
-            for (auto &u : d->run) {
-                poison_host(true, u.in, in_bytes);
-                poison_host(true, u.pcm, K * 2304 * sizeof(float));
-                poison_host(true, u.inf, K * sizeof(mp3d_frame_info));
-            }
+            if (u.in.alloc(in_bytes, hipHostMallocMapped, poison) != hipSuccess || u.in.map() != hipSuccess ||
+                u.pcm.alloc(K * 2304 * sizeof(float), co, poison) != hipSuccess ||
+                u.inf.alloc(K * sizeof(mp3d_frame_info), co, poison) != hipSuccess ||
+                u.snap.grow(d->b, sizeof(StreamState)) != MP3D_OK || u.pcm.map() != hipSuccess ||
+                u.inf.map() != hipSuccess || u.done.create(hipEventDisableTiming) != hipSuccess)
+                return fail(MP3D_E_NOMEM);
     } else {
         d->ra_max = 0;
     }
@@ -283,23 +242,19 @@ extern "C" void mp3d_dec_reset(mp3d_dec *d) {
 
 extern "C" int mp3d_dec_set_options(mp3d_dec *d, int flags) {
     if (!d) return MP3D_E_ARG;
-    const int r = ra_settle(d); /* frames read ahead under the old options */
-    if (r) return r;
+    RCCHK(ra_settle(d)); /* frames read ahead under the old options */
     return mp3d_batch_set_options(d->b, flags);
 }
 
 extern "C" int mp3d_dec_stream_info(mp3d_dec *d, mp3d_stream_info *out) {
     if (!d || !out) return MP3D_E_ARG;
-    {
-        const int rj = ra_join(d);
-        if (rj) return rj;
-    }
+    RCCHK(ra_join(d));
     return mp3d_batch_stream_info(d->b, 1, out);
 }
 
 /* One frame through k_frame (one launch), then a poll of the mapped
  * completion word instead of a stream sync (~5 us less per
- * call).  The frame is in d->h_in[0, have).  Every few thousand polls a
+ * call).  The frame is in d->in[0, have).  Every few thousand polls a
  * stream query catches a kernel that faulted or aborted; a kernel that
  * never completes keeps the stream busy, so after ~1 ms of polling the host
  * stops spinning and blocks in hipStreamSynchronize (a hung kernel then
@@ -307,29 +262,27 @@ extern "C" int mp3d_dec_stream_info(mp3d_dec *d, mp3d_stream_info *out) {
 static int pf_fused(mp3d_dec *d, uint32_t have, bool f32, bool lsf) {
     mp3d_batch *b = d->b;
     hipStream_t s = b->own;
-    int r = call_begin(b, s);
-    if (r) return r;
+    RCCHK(call_begin(b, s));
     CallEnd done{b, s};
     const uint64_t off = 0;
     const uint32_t sz = MP3D_PF_BYTES;
-    r = prepare_geometry(b, &off, &sz, 1, s); /* uploaded once, then cached */
-    if (!r) r = flush_tail(b, s); /* k_frame reads the state from StreamState */
-    if (r) return r;
-    const mp3d_batch::Geo &g = b->geo[b->geo_i];
+    RCCHK(prepare_geometry(b, &off, &sz, 1, s)); /* uploaded once, then cached */
+    RCCHK(flush_tail(b, s));                     /* k_frame reads the state from StreamState */
+    mp3d_batch::Geo &g = b->geo[b->geo_i];
     const uint32_t seq = ++d->seq ? d->seq : ++d->seq; /* never 0, the word's initial value */
-    if (b->poison) launch_lds_poison(g_dev[b->device].n_cu, s);
-    launch_frame(d->m_in, have, g.in_off(), g.in_len(), b->md, g.md_off(), b->st, b->rec, b->sideu, d->m_info,
-                 b->opts, g_dev[b->device].tables, b->is_buf, b->meta, d->m_out, f32, lsf, d->m_done, seq, s);
-    HIPCHK(hipGetLastError());
-    b->geo[b->geo_i].fresh = false; /* no event per call here: end_event covers it */
+    RCCHK(stage_launch(b, nullptr, s, [&] {
+        launch_frame(d->in.m, have, g.in_off(), g.in_len(), b->md, g.md_off(), b->st, b->rec, b->sideu, d->info.m,
+                     b->opts, g_dev[b->device].tables, b->is_buf, b->meta, d->out.m, f32, lsf, d->done.m, seq, s);
+    }));
+    g.fresh = false; /* no event per call here: end_event covers it */
     for (uint32_t n = 1;; n++) {
-        if (__atomic_load_n(d->h_done, __ATOMIC_ACQUIRE) == seq) return MP3D_OK;
+        if (__atomic_load_n(d->done.p, __ATOMIC_ACQUIRE) == seq) return MP3D_OK;
         if ((n & 4095u) == 0) {
             const hipError_t e = n >= (64u << 12) ? hipStreamSynchronize(s) : hipStreamQuery(s);
             if (e == hipErrorNotReady) continue;
             HIPCHK(e);
             /* the stream is idle: the word must be there now */
-            if (__atomic_load_n(d->h_done, __ATOMIC_ACQUIRE) == seq) return MP3D_OK;
+            if (__atomic_load_n(d->done.p, __ATOMIC_ACQUIRE) == seq) return MP3D_OK;
             return MP3D_E_HIP;
         }
     }
@@ -349,10 +302,7 @@ static int ra_settle(mp3d_dec *d) {
     return r;
 }
 static int ra_settle_(mp3d_dec *d) {
-    {
-        const int rj = ra_join(d); /* a launch still on the helper thread */
-        if (rj) return rj;
-    }
+    RCCHK(ra_join(d)); /* a launch still on the helper thread */
     mp3d_dec::Run &c = d->R(), &n = d->N();
     if (c.ents.empty() && n.ents.empty()) return MP3D_OK;
     const size_t served = d->ra_next;
@@ -366,8 +316,7 @@ static int ra_settle_(mp3d_dec *d) {
     d->ra_cool = d->ra_backoff;
     mp3d_batch *b = d->b;
     HIPCHK(hipSetDevice(b->device));
-    int r = own_after_last(b); /* (the next run, if any, is on the own stream before this) */
-    if (r) return r;
+    RCCHK(own_after_last(b)); /* (the next run, if any, is on the own stream before this) */
     b->tail_live = -1; /* the tail holds the state after the last run */
     if (cur_all) {
         HIPCHK(hipMemcpyAsync(b->st, n.snap, sizeof(StreamState), hipMemcpyDeviceToDevice, b->own));
@@ -375,12 +324,12 @@ static int ra_settle_(mp3d_dec *d) {
     } else {
         HIPCHK(hipMemcpyAsync(b->st, c.snap, sizeof(StreamState), hipMemcpyDeviceToDevice, b->own));
         if (served) {
-            const uint64_t off = 0;
             const uint32_t len = c.ents[served - 1].off + c.ents[served - 1].len;
-            const FpRun fp = {c.in_m, len, (const uint32_t *)(c.in + c.fo_at), nullptr, c.snap};
-            r = batch_decode(b, c.in_m, &off, &len, 1, (int)served, c.pcm_m, c.f32, c.inf_m, nullptr, true, 3, true,
-                             d->ra_seg, &fp, false);
-            if (r) return r;
+            const FpRun fp = {c.in.m, len, (const uint32_t *)(c.in + c.fo_at), nullptr, c.snap};
+            DecodeCall k;
+            k.n = 1, k.F = (int)served, k.pcm = c.pcm.m, k.f32 = c.f32, k.infos = c.inf.m;
+            k.mapped = true, k.seg_len = d->ra_seg, k.fp = &fp;
+            RCCHK(batch_decode(b, k));
         } else {
             HIPCHK(hipStreamSynchronize(b->own));
         }
@@ -434,17 +383,16 @@ static int ra_stage(mp3d_dec *d, mp3d_dec::Run &u, const uint8_t *buf, size_t by
 static int ra_launch(mp3d_dec *d, mp3d_dec::Run &u, uint32_t o, int kinds, bool f32, bool async) {
     mp3d_batch *b = d->b;
     HIPCHK(hipSetDevice(b->device));
-    int r = own_after_last(b);
-    if (r) return r;
+    RCCHK(own_after_last(b));
     /* the previous run's synthesis tail is flushed into the state, and the
      * state before this run saved to u.snap (for ra_settle), by k_demux_fp */
     const float *tail = b->tail_live >= 0 ? b->st_tail[b->tail_live].p : nullptr;
     b->tail_live = -1;
-    const uint64_t off = 0;
-    const FpRun fp = {u.in_m, o, (const uint32_t *)(u.in + u.fo_at), tail, u.snap};
-    r = batch_decode(b, u.in_m, &off, &o, 1, (int)u.ents.size(), u.pcm_m, f32, u.inf_m, nullptr, true, kinds, true,
-                     d->ra_seg, &fp, async);
-    if (r) return r;
+    const FpRun fp = {u.in.m, o, (const uint32_t *)(u.in + u.fo_at), tail, u.snap};
+    DecodeCall k;
+    k.n = 1, k.F = (int)u.ents.size(), k.pcm = u.pcm.m, k.f32 = f32, k.infos = u.inf.m;
+    k.kinds = kinds, k.mapped = true, k.seg_len = d->ra_seg, k.fp = &fp, k.async = async;
+    RCCHK(batch_decode(b, k));
     if (async && d->dbg_fail && ++d->dbg_launches == d->dbg_fail) {
         (void)hipStreamSynchronize(b->own);
         return MP3D_E_HIP;
@@ -551,16 +499,12 @@ static int decode_frame(mp3d_dec *d, const uint8_t *buf, size_t bytes, void *pcm
                !memcmp(buf + pos, u.in + e.off, e.len);
     };
     if (d->ra_next < d->R().ents.size()) {
-        if (!same(d->R(), d->R().ents[d->ra_next])) {
-            const int r = ra_settle(d);
-            if (r) return r;
-        }
+        if (!same(d->R(), d->R().ents[d->ra_next])) RCCHK(ra_settle(d));
     } else if (!d->R().ents.empty()) {
         /* the run being served is used up: on to the next run when this call
          * asks for its first frame (it was decoding behind the served calls),
          * and launch the one after it */
-        const int rj = ra_join(d); /* the helper's launch of it (its status) */
-        if (rj) return rj;
+        RCCHK(ra_join(d)); /* the helper's launch of it (its status) */
         mp3d_dec::Run &n = d->N();
         if (!n.ents.empty() && same(n, n.ents[0])) {
             if (n.pending) HIPCHK(hipEventSynchronize(n.done));
@@ -569,11 +513,9 @@ static int decode_frame(mp3d_dec *d, const uint8_t *buf, size_t bytes, void *pcm
             d->cur ^= 1;
             d->ra_next = 0;
             d->ra_backoff = 0;
-            const int r = ra_launch_next(d, buf, bytes, f32);
-            if (r) return r;
+            RCCHK(ra_launch_next(d, buf, bytes, f32));
         } else {
-            const int r = ra_settle(d); /* (served whole: a no-op unless a next run is dropped) */
-            if (r) return r;
+            RCCHK(ra_settle(d)); /* (served whole: a no-op unless a next run is dropped) */
         }
     }
     if (loc <= 0) {
@@ -581,10 +523,7 @@ static int decode_frame(mp3d_dec *d, const uint8_t *buf, size_t bytes, void *pcm
         return loc;
     }
     bool cached = d->ra_next < d->R().ents.size();
-    if (!cached) { /* the batch handle is used below */
-        const int rj = ra_join(d);
-        if (rj) return rj;
-    }
+    if (!cached) RCCHK(ra_join(d)); /* the batch handle is used below */
     if (!cached && have == (size_t)fb && d->ra_max) {
         if (d->ra_cool > 0) { /* backing off after a wasted read-ahead */
             d->ra_cool--;
@@ -595,8 +534,7 @@ static int decode_frame(mp3d_dec *d, const uint8_t *buf, size_t bytes, void *pcm
             cached = r == 1;
             if (cached) {
                 d->ra_next = 0;
-                const int r2 = ra_launch_next(d, buf, bytes, f32);
-                if (r2) return r2;
+                RCCHK(ra_launch_next(d, buf, bytes, f32));
             }
         }
     }
@@ -608,25 +546,26 @@ static int decode_frame(mp3d_dec *d, const uint8_t *buf, size_t bytes, void *pcm
         out = (const uint8_t *)c.pcm + d->ra_next * 2304 * (f32 ? sizeof(float) : sizeof(int16_t));
         d->ra_next++;
     } else {
-        uint64_t off = 0;
-        uint32_t sz = MP3D_PF_BYTES;
-        memcpy(d->h_in, buf + pos, have); /* have <= fb <= MP3D_MAX_FRAME_BYTES */
-        int r;
+        const uint64_t off = 0;
+        const uint32_t sz = MP3D_PF_BYTES;
+        memcpy(d->in, buf + pos, have); /* have <= fb <= MP3D_MAX_FRAME_BYTES */
+        const int kind = host_frame_kind(buf + pos); /* 1 MPEG-1, 2 LSF */
         if (d->fused) {
-            r = pf_fused(d, (uint32_t)have, f32, host_frame_kind(buf + pos) == 2);
+            RCCHK(pf_fused(d, (uint32_t)have, f32, kind == 2));
         } else {
-            memset(d->h_in + have, 0, MP3D_PF_BYTES - have);
+            memset(d->in + have, 0, MP3D_PF_BYTES - have);
             /* mapped pinned buffers: the kernels read the frame and write PCM +
-             * info in place (three launches + one sync); else staged copies */
-            const bool mapped = d->m_in != nullptr;
-            r = mapped ? batch_decode(d->b, d->m_in, &off, &sz, 1, 1, d->m_out, f32, d->m_info, nullptr, true,
-                                      host_frame_kind(buf + pos), true, 0, nullptr, false)
-                       : batch_decode(d->b, d->h_in, &off, &sz, 1, 1, d->h_out, f32, d->h_info, nullptr, true,
-                                      host_frame_kind(buf + pos), false, 0, nullptr, false); /* 1 MPEG-1, 2 LSF */
+             * info in place (three launches + one sync); else staged copies
+             * of the whole row (only its audio is read below) */
+            const bool mapped = d->in.m != nullptr;
+            DecodeCall k;
+            k.frames = mapped ? d->in.m : d->in.p, k.offsets = &off, k.sizes = &sz, k.n = 1, k.F = 1;
+            k.pcm = mapped ? d->out.m : d->out.p, k.f32 = f32, k.infos = mapped ? d->info.m : d->info.p;
+            k.clobber_unwritten = true, k.kinds = kind, k.mapped = mapped;
+            RCCHK(batch_decode(d->b, k));
         }
-        if (r) return r;
-        fi = *d->h_info;
-        out = d->h_out;
+        fi = *d->info.p;
+        out = d->out.p;
     }
     d->frames++;
     if (fi.frame_bytes) d->kind = host_frame_kind(buf + pos);
@@ -653,23 +592,18 @@ extern "C" int mp3d_decode_frame_ex(mp3d_dec *d, const uint8_t *buf, size_t byte
 
 extern "C" int mp3d_dec_get_state(mp3d_dec *d, void *buf) {
     if (!d) return MP3D_E_ARG;
-    const int r = ra_settle(d); /* the state after the frames served, not after those read ahead */
-    if (r) return r;
+    RCCHK(ra_settle(d)); /* the state after the frames served, not after those read ahead */
     return mp3d_batch_get_state(d->b, 0, 1, buf);
 }
 
 extern "C" int mp3d_dec_set_state(mp3d_dec *d, const void *buf) {
     if (!d || !buf) return MP3D_E_ARG;
-    {
-        /* a refused blob writes nothing (mp3d.h): checked BEFORE the read-ahead
-         * is forgotten, so the decoder stays at the frame it served */
-        (void)ra_join(d); /* (a failed launch left d->broken, which a new state clears) */
-        const int rb = blob_check(d->b, 1, buf);
-        if (rb) return rb;
-    }
+    /* a refused blob writes nothing (mp3d.h): checked BEFORE the read-ahead
+     * is forgotten, so the decoder stays at the frame it served */
+    (void)ra_join(d); /* (a failed launch left d->broken, which a new state clears) */
+    RCCHK(blob_check(d->b, 1, buf));
     ra_drop(d); /* replaced whole: nothing read ahead applies */
-    const int r = mp3d_batch_set_state(d->b, 0, 1, buf);
-    if (r) return r;
+    RCCHK(mp3d_batch_set_state(d->b, 0, 1, buf));
     d->broken = 0; /* a whole new state: a failed read-ahead no longer matters */
     /* host mirror of the family lock and "past the stream start" (ID3v2 skip) */
     StreamState h;

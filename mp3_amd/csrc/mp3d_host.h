@@ -3,10 +3,14 @@
  * mp3d_batch.cpp, mp3d_long.cpp, mp3d_dec.cpp, mp3d_sinks.cpp,
  * mp3d_loudness.cpp, mp3d_normalize.cpp, mp3d_stretch.cpp, mp3d_limiter.cpp,
  * mp3d_segment.cpp):
- * the error macros, the owning device buffer, the batch handle, the frame
- * that the calls of the stages behind the packed sink share, and the internal
- * functions that cross those files.  Nothing here is exported (the library
- * is built with hidden visibility; the C ABI is include/mp3d.h).
+ * the error macros, the readers of the environment's knobs, the owning types
+ * (DevBuf device memory, PinBuf pinned host memory, Event), the batch handle,
+ * the frame that every call shares -- the core decode (DecodeCall,
+ * core_launch), the long-stream calls, the per-frame decoder and the stages
+ * behind the packed sink (stage_launch, set_begin / set_end, CallerOut,
+ * CallEnd) -- and the internal functions that cross those files.  Nothing
+ * here is exported (the library is built with hidden visibility; the C ABI is
+ * include/mp3d.h).
  */
 #ifndef MP3D_HOST_H
 #define MP3D_HOST_H
@@ -49,6 +53,24 @@ inline int hip_rc(hipError_t e) {
         if (const int _rc = (x)) return _rc;                                                                           \
     } while (0)
 #define HIPCHK(x) RCCHK(mp3d::hip_rc(x))
+
+/* The environment's knobs are read through these four and nowhere else.
+ * env_set: set to anything, the empty word included; env_flag: set and
+ * neither empty nor "0"; env_is: set to this word; env_int: an integer
+ * (atoi) clamped to [lo, hi], dflt when unset. */
+inline bool env_set(const char *name) { return getenv(name) != nullptr; }
+inline bool env_flag(const char *name) {
+    const char *e = getenv(name);
+    return e && e[0] && strcmp(e, "0") != 0;
+}
+inline bool env_is(const char *name, const char *word) {
+    const char *e = getenv(name);
+    return e && !strcmp(e, word);
+}
+inline int env_int(const char *name, int dflt, int lo, int hi) {
+    const char *e = getenv(name);
+    return e ? std::max(lo, std::min(hi, atoi(e))) : dflt;
+}
 
 /* per-device one-time init: constant symbols + table buffer (mp3d_host_tables.cpp) */
 struct DeviceCtx {
@@ -94,13 +116,61 @@ template <class T> struct DevBuf {
     operator T *() const { return p; }
 };
 
+/* One pinned host allocation, freed with its owner, and its device address
+ * when it was mapped (m = null: the device reaches it through copies only). */
+template <class T> struct PinBuf {
+    T *p = nullptr, *m = nullptr;
+    PinBuf() = default;
+    PinBuf(const PinBuf &) = delete;
+    PinBuf &operator=(const PinBuf &) = delete;
+    ~PinBuf() {
+        if (p) (void)hipHostFree(p);
+    }
+    /* `bytes` with hipHostMalloc's `flags`, filled with 0xFF when `poison` */
+    hipError_t alloc(size_t bytes, unsigned flags, bool poison) {
+        const hipError_t e = hipHostMalloc((void **)&p, bytes, flags);
+        poison_host(poison && e == hipSuccess, p, bytes);
+        return e;
+    }
+    /* m = the device address; after a failure m is null */
+    hipError_t map() {
+        const hipError_t e = hipHostGetDevicePointer((void **)&m, p, 0);
+        if (e != hipSuccess) m = nullptr;
+        return e;
+    }
+    operator T *() const { return p; }
+};
+
+/* One event, destroyed with its owner (after the owner's waits).  An
+ * ordering event is made by create() when its owner is; a timing event is
+ * made by the first record_timed(), so a handle that never times has none
+ * and a failed creation is the error of the call that needed the event. */
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(const Event &) = delete;
+    Event &operator=(const Event &) = delete;
+    ~Event() {
+        if (e) (void)hipEventDestroy(e);
+    }
+    hipError_t create(unsigned flags) { return hipEventCreateWithFlags(&e, flags); }
+    hipError_t record_timed(hipStream_t s) {
+        if (!e) {
+            const hipError_t r = create(hipEventDefault);
+            if (r != hipSuccess) return r;
+        }
+        return hipEventRecord(e, s);
+    }
+    operator hipEvent_t() const { return e; }
+};
+
 /* one timed stage of a call (mp3d_batch_set_timing): an event on each side */
 struct StageTimer {
-    hipEvent_t ev[2] = {};
+    Event ev[2];
     bool timed = false; /* ev hold a call's stage */
-    hipError_t begin(hipStream_t s) { return hipEventRecord(ev[0], s); }
+    hipError_t begin(hipStream_t s) { return ev[0].record_timed(s); }
     hipError_t end(hipStream_t s) {
-        const hipError_t e = hipEventRecord(ev[1], s);
+        const hipError_t e = ev[1].record_timed(s);
         timed = timed || e == hipSuccess;
         return e;
     }
@@ -152,10 +222,10 @@ struct mp3d_batch {
      * in_len[n] u32. */
     struct Geo {
         mp3d::DevBuf<uint64_t> d;
-        uint64_t *h = nullptr;       /* pinned */
-        hipEvent_t staged = nullptr; /* the copy h -> d is complete        */
-        hipEvent_t freed = nullptr;  /* the last kernel reading d is done */
-        bool fresh = false;          /* freed recorded by the slot's last reader */
+        mp3d::PinBuf<uint64_t> h;
+        mp3d::Event staged; /* the copy h -> d is complete        */
+        mp3d::Event freed;  /* the last kernel reading d is done */
+        bool fresh = false; /* freed recorded by the slot's last reader */
         int n = -1;
         uint64_t *in_off() const { return d; }
         uint64_t *md_off() const { return d + n; }
@@ -191,9 +261,12 @@ struct mp3d_batch {
      * destroyed since), and a call on another stream is ordered after it.
      * Calls on the handle's own stream (the per-frame decoder) record
      * nothing: own-stream order covers them. */
-    hipEvent_t ev_done = nullptr;
+    mp3d::Event ev_done;
     hipStream_t last_s = nullptr; /* compared with the next call's, never used */
-    hipEvent_t ev[4] = {};
+    /* the core decode's timing (mp3d_batch_kernel_times), a chain on the
+     * call's stream: before demux, after demux, after Huffman, after
+     * synthesis (core_mark, core_launch) */
+    mp3d::Event ev[4];
     /* packed PCM sink (mp3d_batch_set_output; mp3d_resample.h): f.hz = 0 is
      * off, and then none of these buffers exists.  st, plan, cnt hold
      * max_streams entries; rows (the float32 rows of a packed call), prefix
@@ -388,9 +461,8 @@ PtrKind ptr_kind(const void *p, int device);
 inline bool is_device_ptr(const void *p, int device) { return ptr_kind(p, device) == PTR_DEV; }
 
 /* The stages downstream of the packed sink, listed once. A new sink adds its
- * line to stages_off and to stages_restart, and its timer to the two loops
- * over the timers in mp3d_batch.cpp (create, destroy); nothing else names
- * them all. */
+ * line to stages_off and to stages_restart; nothing else names them all (a
+ * stage's timer owns its events). */
 /* they read the packed sink's format: off with any change of it */
 inline void stages_off(mp3d_batch *b) {
     b->ft.off(), b->ld.off(), b->nm.off(), b->ga.off(), b->sx.off(), b->lm.off(), b->sg.off();
@@ -409,7 +481,8 @@ inline int stages_restart(mp3d_batch *b, int first, int n, hipStream_t s) {
     return MP3D_OK;
 }
 
-/* ---- the frame of a stage's calls ---- */
+/* ---- the frame of a stage's calls, which the core
+ * decode, the long-stream calls and the per-frame decoder use too ---- */
 /* the head of a set_* call: the handle idle, its last call done */
 inline int set_begin(mp3d_batch *b) {
     HIPCHK(hipSetDevice(b->device));
@@ -436,6 +509,31 @@ template <class F> int stage_launch(mp3d_batch *b, StageTimer *tm, hipStream_t s
     launch();
     if (tm) HIPCHK(tm->end(s));
     return hip_rc(hipGetLastError());
+}
+
+/* event i of the core decode's timing chain (mp3d_batch.ev) on stream s, when
+ * the handle times */
+inline int core_mark(mp3d_batch *b, int i, hipStream_t s) {
+    if (b->timing) HIPCHK(b->ev[i].record_timed(s));
+    return MP3D_OK;
+}
+/* One launch of the core decode on stream s, as a stage's, then event i of
+ * the chain: the time from the event before it is this kernel's */
+template <class F> int core_launch(mp3d_batch *b, int i, hipStream_t s, F &&launch) {
+    RCCHK(stage_launch(b, nullptr, s, launch));
+    return core_mark(b, i, s);
+}
+
+/* The tail the per-slot setters share (mp3d_batch_set_window, _set_tempo,
+ * _set_segment_threshold), after a setter's own validation: the own stream
+ * ordered after the handle's last call, on any stream; `queue(s)`, the
+ * setter's copy of its parameters and restart of the slots' state, in the
+ * setter's order; and the wait (the parameters are on the setter's stack). */
+template <class F> int slots_set(mp3d_batch *b, F &&queue) {
+    HIPCHK(hipSetDevice(b->device));
+    RCCHK(own_after_last(b));
+    RCCHK(queue(b->own));
+    return hip_rc(hipStreamSynchronize(b->own));
 }
 
 /* behind the *_time exports */
@@ -504,16 +602,41 @@ struct FpRun {
     const float *tail_in; /* the handle's live synthesis tail, or null     */
     StreamState *snap;   /* receives the state before the run             */
 };
-/* decode into int16 (f32 = false) or float32 PCM, both [n][F][2304] */
-/* kinds: k_synth family variants to launch (bit 0 MPEG-1, bit 1 LSF); 3 for
- * a batch, one bit for the per-frame decoder, which knows its frame's family */
-/* mapped: frames, pcm and infos are device-accessible pinned host memory
- * (the per-frame decoder): the kernels read and write them in place and the
- * call ends with one stream sync */
-/* async (mapped only): return without waiting; the caller records an event */
-int batch_decode(mp3d_batch *b, const uint8_t *frames, const uint64_t *offsets, const uint32_t *sizes, int n, int F,
-                 void *pcm, bool f32, mp3d_frame_info *infos, void *hip_stream, bool overwrite, int kinds = 3,
-                 bool mapped = false, int seg_len_req = 0, const FpRun *fp = nullptr, bool async = false);
+/* One call of the core decode (demux, Huffman, synthesis), filled by field
+ * name: the public decodes leave the options at their defaults. */
+struct DecodeCall {
+    /* input: stream i is sizes[i] bytes at frames + offsets[i]; n streams, F frames of each */
+    const uint8_t *frames = nullptr;
+    const uint64_t *offsets = nullptr;
+    const uint32_t *sizes = nullptr;
+    int n = 0, F = 0;
+    /* sink: PCM [n][F][2304], int16 or (f32) float32; frame infos [n][F] or
+     * null; the caller's stream, or null for the handle's own */
+    void *pcm = nullptr;
+    bool f32 = false;
+    mp3d_frame_info *infos = nullptr;
+    void *hip_stream = nullptr;
+    /* A host PCM buffer is read back whole.  false: the bytes the kernels
+     * did not write (rows without audio, the second half of a mono / LSF
+     * row) are saved from the caller's buffer first and put back; true: they
+     * are not (an internal caller that reads only the rows' audio). */
+    bool clobber_unwritten = false;
+    /* k_synth family variants to launch (bit 0 MPEG-1, bit 1 LSF): 3 for a
+     * batch, one bit for the per-frame decoder, which knows its frame's family */
+    int kinds = 3;
+    /* frames, pcm and infos are device-accessible pinned host memory (the
+     * per-frame decoder): the kernels read and write them in place and the
+     * call ends with one stream sync */
+    bool mapped = false;
+    /* frames per synthesis segment; 0: chosen from n and F */
+    int seg_len = 0;
+    /* the front half runs on these pre-located frames of one stream (then
+     * frames, offsets and sizes are not read) */
+    const FpRun *fp = nullptr;
+    /* return without waiting (mapped only, else MP3D_E_ARG); the caller records an event */
+    bool async = false;
+};
+int batch_decode(mp3d_batch *b, const DecodeCall &c);
 
 /* ---- mp3d_sinks.cpp ---- */
 extern const int RS_RATES[MP3D_RS_RATES];

@@ -14,8 +14,7 @@ extern "C" int mp3d_long_plan(const uint8_t *data, size_t bytes, int L, long lon
     std::vector<long long> a;
     int wmax = 0;
     *n_frames = 0;
-    const int r = long_plan(data, bytes, L, max_frames, off, a, &wmax);
-    if (r) return r;
+    RCCHK(long_plan(data, bytes, L, max_frames, off, a, &wmax));
     *n_frames = (long long)off.size();
     if (frame_off) std::copy(off.begin(), off.end(), frame_off);
     if (seg_start) std::copy(a.begin(), a.end(), seg_start);
@@ -64,8 +63,7 @@ struct LongRun {
             hp = host_copy.data();
         }
         int wmax = 0;
-        const int r = long_plan(hp, bytes, L, max_frames, off, a, &wmax);
-        if (r) return r;
+        RCCHK(long_plan(hp, bytes, L, max_frames, off, a, &wmax));
         N = (long long)off.size();
         K = (long long)a.size();
         F = L + wmax;
@@ -77,26 +75,20 @@ struct LongRun {
         f32 = f32_;
         chunk = chunk_;
         row = 2304 * (f32 ? sizeof(float) : sizeof(int16_t));
-        {
-            int r = own_after_last(b);
-            if (!r) r = flush_tail(b, s); /* before b->st points at the scratch states */
-            if (r) return r;
-        }
+        RCCHK(own_after_last(b));
+        RCCHK(flush_tail(b, s)); /* before b->st points at the scratch states */
         din = data;
         if (!is_device_ptr(data, b->device)) { /* host or another GPU's: staged */
-            int r = b->d_in.grow(b, bytes + 64);
-            if (r) return r;
+            RCCHK(b->d_in.grow(b, bytes + 64));
             HIPCHK(hipMemcpyAsync(b->d_in, data, bytes, hipMemcpyDefault, s));
             din = b->d_in;
         }
         const size_t ns = (size_t)std::min<long long>(chunk, K);
-        int r = seg_pcm.grow(b, ns * F * row);
-        if (!r) r = seg_st.grow(b, sizeof(StreamState) * ns);
-        if (r) return r;
+        RCCHK(seg_pcm.grow(b, ns * F * row));
+        RCCHK(seg_st.grow(b, sizeof(StreamState) * ns));
         b->st = seg_st;
         swapped = true;
-        r = d_a.grow(b, sizeof(int) * K);
-        if (r) return r;
+        RCCHK(d_a.grow(b, sizeof(int) * K));
         a32.assign(a.begin(), a.end());
         HIPCHK(hipMemcpyAsync(d_a, a32.data(), sizeof(int) * K, hipMemcpyHostToDevice, s));
         return MP3D_OK;
@@ -114,7 +106,10 @@ struct LongRun {
         /* fresh decoder state for every virtual stream */
         HIPCHK(state_clear(b->st, ns, s));
         b->tail_live = -1; /* fresh states: no tail of the previous chunk */
-        return batch_decode(b, din, so.data(), ss.data(), ns, F, seg_pcm, f32, nullptr, s, false);
+        DecodeCall c; /* no infos for the caller: they stay in b->d_infos */
+        c.frames = din, c.offsets = so.data(), c.sizes = ss.data(), c.n = ns, c.F = F;
+        c.pcm = seg_pcm, c.f32 = f32, c.hip_stream = s;
+        return batch_decode(b, c);
     }
 };
 
@@ -130,26 +125,21 @@ extern "C" int mp3d_batch_decode_long(mp3d_batch *b, const uint8_t *data, size_t
     DevBuf<void> out_pcm;
     DevBuf<mp3d_frame_info> out_inf;
     LongRun R(b);
-    int r = R.plan(data, bytes, L, max_frames);
-    if (r) return r;
+    RCCHK(R.plan(data, bytes, L, max_frames));
     const long long N = R.N;
     *n_frames = N;
     if (N == 0) return MP3D_OK;
     hipStream_t s = R.s;
-    r = R.open(f32 != 0, b->max_streams);
-    if (r) return r;
+    RCCHK(R.open(f32 != 0, b->max_streams));
     const size_t row = R.row;
-    if (!pcm_dev) r = out_pcm.grow(b, (size_t)N * row);
-    if (!r && infos && !inf_dev) r = out_inf.grow(b, sizeof(mp3d_frame_info) * (size_t)N);
-    if (r) return r;
+    if (!pcm_dev) RCCHK(out_pcm.grow(b, (size_t)N * row));
+    if (infos && !inf_dev) RCCHK(out_inf.grow(b, sizeof(mp3d_frame_info) * (size_t)N));
     void *dpcm = pcm_dev ? pcm : out_pcm.p;
     mp3d_frame_info *dinf = inf_dev ? infos : out_inf.p; /* (null without infos) */
     for (long long k0 = 0; k0 < R.K; k0 += R.chunk) {
         const int ns = R.segments(k0);
-        r = R.decode_chunk(k0);
-        if (r) return r;
-        if (k0 == 0 && sinfo) r = mp3d_batch_stream_info(b, 1, sinfo);
-        if (r) return r;
+        RCCHK(R.decode_chunk(k0));
+        if (k0 == 0 && sinfo) RCCHK(mp3d_batch_stream_info(b, 1, sinfo));
         const long long j0 = k0 * L, j1 = std::min(N, (k0 + ns) * L);
         launch_gather_frames(R.seg_pcm, (uint8_t *)dpcm + (size_t)j0 * row, b->d_infos, dinf ? dinf + j0 : nullptr,
                              R.d_a + k0, L, R.F, (int)k0, (int)(j1 - j0), (int)row, s);
@@ -202,19 +192,16 @@ extern "C" int mp3d_batch_decode_long_packed(mp3d_batch *b, const uint8_t *data,
     DevBuf<int32_t> d_prefix;
     DevBuf<void> d_out; /* the device image of a host out */
     LongRun R(b);
-    int r = R.plan(data, bytes, L, 0x7fffffffffffffffLL);
-    if (r) return r;
+    RCCHK(R.plan(data, bytes, L, 0x7fffffffffffffffLL));
     if (R.N == 0) return MP3D_OK;
     hipStream_t s = R.s;
-    r = R.open(true, (int)std::min<long long>(b->max_streams, lim));
-    if (r) return r;
+    RCCHK(R.open(true, (int)std::min<long long>(b->max_streams, lim)));
     /* the filters: the sink's own when its rate matches, else those of the
      * last call of this kind (the sink's stay as they are) */
     const RsFilters *flt = &b->rs.f;
     if (flt->hz != out_hz) {
         flt = &b->lp;
-        if (flt->hz != out_hz) r = b->lp.upload(b, out_hz, 0, s);
-        if (r) return r;
+        if (flt->hz != out_hz) RCCHK(b->lp.upload(b, out_hz, 0, s));
     }
     /* blocks per chunk: enough tiles for the most a chunk of any input rate
      * can emit (its inputs plus a pending tail) */
@@ -227,28 +214,24 @@ extern "C" int mp3d_batch_decode_long_packed(mp3d_batch *b, const uint8_t *data,
     }
     if (tiles > 0x7fffffffLL) return MP3D_E_CAPACITY;
     const long long cap = out_dev ? out_cap : std::min(out_cap, whole);
-    r = d_st.grow(b, sizeof(RsLong));
-    if (!r) r = d_prefix.grow(b, sizeof(int32_t) * (size_t)(nf_max + 1));
-    if (!r && !out_dev && cap > 0) r = d_out.grow(b, eb * (size_t)cap);
-    if (r) return r;
+    RCCHK(d_st.grow(b, sizeof(RsLong)));
+    RCCHK(d_prefix.grow(b, sizeof(int32_t) * (size_t)(nf_max + 1)));
+    if (!out_dev && cap > 0) RCCHK(d_out.grow(b, eb * (size_t)cap));
     HIPCHK(hipMemsetAsync(d_st, 0, sizeof(RsLong), s)); /* the stream's start */
     void *dout = out_dev ? out : d_out.p;
     for (long long k0 = 0; k0 < R.K; k0 += R.chunk) {
         const int ns = R.segments(k0);
-        r = R.decode_chunk(k0);
-        if (r) return r;
-        if (k0 == 0 && sinfo) r = mp3d_batch_stream_info(b, 1, sinfo);
-        if (r) return r;
+        RCCHK(R.decode_chunk(k0));
+        if (k0 == 0 && sinfo) RCCHK(mp3d_batch_stream_info(b, 1, sinfo));
         const long long j0 = k0 * L, j1 = std::min(R.N, (k0 + ns) * L);
-        if (b->timing) HIPCHK(b->rs.tm.begin(s));
-        if (b->poison) launch_lds_poison(g_dev[b->device].n_cu, s);
         /* (the tag words of virtual stream 0 are read by the first chunk's
-         * plan, before the next chunk clears the states) */
-        launch_resample_long((const float *)R.seg_pcm.p, b->d_infos, R.d_a + k0, &R.seg_st[0].tag_info, flt->dcfg, oc,
-                             flt->tab, d_st, d_prefix, dout, f32 != 0, cap, L, R.F, (int)k0, (int)(j1 - j0), (int)tiles,
-                             k0 == 0, k0 + ns >= R.K, (flags & MP3D_LONG_GAPLESS) ? 1 : 0, s);
-        if (b->timing) HIPCHK(b->rs.tm.end(s)); /* mp3d_batch_resample_time: the last chunk's stage */
-        HIPCHK(hipGetLastError());
+         * plan, before the next chunk clears the states; mp3d_batch_resample_time:
+         * the last chunk's stage) */
+        RCCHK(stage_launch(b, &b->rs.tm, s, [&] {
+            launch_resample_long((const float *)R.seg_pcm.p, b->d_infos, R.d_a + k0, &R.seg_st[0].tag_info, flt->dcfg,
+                                 oc, flt->tab, d_st, d_prefix, dout, f32 != 0, cap, L, R.F, (int)k0, (int)(j1 - j0),
+                                 (int)tiles, k0 == 0, k0 + ns >= R.K, (flags & MP3D_LONG_GAPLESS) ? 1 : 0, s);
+        }));
     }
     RsLong end;
     HIPCHK(hipMemcpyAsync(&end, d_st, offsetof(RsLong, hist), hipMemcpyDeviceToHost, s));

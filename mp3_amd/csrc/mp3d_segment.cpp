@@ -79,15 +79,12 @@ extern "C" int mp3d_batch_set_segment_threshold(mp3d_batch *b, int first, int n,
         if (thr[i] < 1 || thr[i] > sg_full(b->sg.H)) return MP3D_E_ARG; /* before anything is written */
         t[i] = thr[i];
     }
-    HIPCHK(hipSetDevice(b->device));
-    hipStream_t s = b->own;
-    int r = own_after_last(b); /* after the handle's last call, on any stream */
-    if (r) return r;
-    HIPCHK(hipMemcpyAsync(b->sg.thr + first, t.data(), sizeof(uint64_t) * t.size(), hipMemcpyHostToDevice, s));
-    /* a new threshold is a new stream: the slots' segment state restarts */
-    HIPCHK(hipMemsetAsync(b->sg.st + first, 0, sizeof(SgState) * (size_t)n, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return MP3D_OK;
+    return slots_set(b, [&](hipStream_t s) -> int {
+        HIPCHK(hipMemcpyAsync(b->sg.thr + first, t.data(), sizeof(uint64_t) * t.size(), hipMemcpyHostToDevice, s));
+        /* a new threshold is a new stream: the slots' segment state restarts */
+        HIPCHK(hipMemsetAsync(b->sg.st + first, 0, sizeof(SgState) * (size_t)n, s));
+        return MP3D_OK;
+    });
 }
 
 /* The segment stage on stream s: dsmp [n][sstride][channels] samples and dcin

@@ -140,9 +140,8 @@ int RsFilters::upload(const mp3d_batch *b, int out_hz, int out_channels, hipStre
     std::vector<float> t;
     rs_build(out_hz, out_channels, c, t);
     hz = 0; /* none until the new ones are on the device */
-    int r = dcfg.grow(b, sizeof(RsCfg));
-    if (!r) r = tab.grow(b, sizeof(float) * t.size());
-    if (r) return r;
+    RCCHK(dcfg.grow(b, sizeof(RsCfg)));
+    RCCHK(tab.grow(b, sizeof(float) * t.size()));
     HIPCHK(hipMemcpyAsync(dcfg, &c, sizeof(c), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(tab, t.data(), sizeof(float) * t.size(), hipMemcpyHostToDevice, s));
     HIPCHK(hipStreamSynchronize(s)); /* (c and t are on this stack) */
@@ -214,14 +213,15 @@ extern "C" int mp3d_batch_decode_packed(mp3d_batch *b, const uint8_t *frames, co
     /* the kernel stores one sample frame (all channels) per instruction: a
      * device sink must be aligned to it (a host sink is filled by copies) */
     if (is_device_ptr(out, b->device) && (uintptr_t)out % (eb * oc)) return MP3D_E_ARG;
-    int r = k.rows.grow(b, sizeof(float) * 2304 * (size_t)n * F);
-    if (!r) r = k.prefix.grow(b, sizeof(int32_t) * (size_t)n * (F + 1));
+    RCCHK(k.rows.grow(b, sizeof(float) * 2304 * (size_t)n * F));
+    RCCHK(k.prefix.grow(b, sizeof(int32_t) * (size_t)n * (F + 1)));
     const bool out_dev = is_device_ptr(out, b->device), cnt_dev = is_device_ptr(out_count, b->device);
-    if (!r && !out_dev) r = k.out.grow(b, eb * oc * (size_t)stride * n + 16);
-    if (r) return r;
+    if (!out_dev) RCCHK(k.out.grow(b, eb * oc * (size_t)stride * n + 16));
     /* the decode itself: the float32 path into the handle's rows */
-    r = batch_decode(b, frames, offsets, sizes, n, F, k.rows, true, infos, hip_stream, false);
-    if (r) return r;
+    DecodeCall c;
+    c.frames = frames, c.offsets = offsets, c.sizes = sizes, c.n = n, c.F = F;
+    c.pcm = k.rows, c.f32 = true, c.infos = infos, c.hip_stream = hip_stream;
+    RCCHK(batch_decode(b, c));
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : b->own;
     CallEnd done{b, s};
     const mp3d_frame_info *dinf = infos && is_device_ptr(infos, b->device) ? infos : b->d_infos.p;
@@ -287,18 +287,15 @@ extern "C" int mp3d_batch_set_window(mp3d_batch *b, int first, int n, const long
             w[i] = RsWindow{0, 1, lo[i], h};
         }
     }
-    HIPCHK(hipSetDevice(b->device));
-    hipStream_t s = b->own;
-    int r = own_after_last(b); /* after the handle's last call, on any stream */
-    if (r) return r;
-    /* a window restart: the slots' resamplers and fed counts restart with it */
-    HIPCHK(hipMemsetAsync(b->rs.st + first, 0, sizeof(RsState) * (size_t)n, s));
-    RCCHK(stages_restart(b, first, n, s));
-    if (lo)
-        HIPCHK(hipMemcpy2DAsync(b->rs.st + first, sizeof(RsState), w.data(), sizeof(RsWindow), sizeof(RsWindow), (size_t)n,
-                                hipMemcpyHostToDevice, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return MP3D_OK;
+    return slots_set(b, [&](hipStream_t s) -> int {
+        /* a window restart: the slots' resamplers and fed counts restart with it */
+        HIPCHK(hipMemsetAsync(b->rs.st + first, 0, sizeof(RsState) * (size_t)n, s));
+        RCCHK(stages_restart(b, first, n, s));
+        if (lo)
+            HIPCHK(hipMemcpy2DAsync(b->rs.st + first, sizeof(RsState), w.data(), sizeof(RsWindow), sizeof(RsWindow),
+                                    (size_t)n, hipMemcpyHostToDevice, s));
+        return MP3D_OK;
+    });
 }
 
 extern "C" int mp3d_batch_sink_window(mp3d_batch *b, int first, int n, long long *lo, long long *hi, long long *fed) {
@@ -310,8 +307,7 @@ extern "C" int mp3d_batch_sink_window(mp3d_batch *b, int first, int n, long long
     };
     std::vector<Head> h((size_t)n);
     HIPCHK(hipSetDevice(b->device));
-    int r = own_after_last(b);
-    if (r) return r;
+    RCCHK(own_after_last(b));
     HIPCHK(hipMemcpy2DAsync(h.data(), sizeof(Head), b->rs.st + first, sizeof(RsState), sizeof(Head), (size_t)n,
                             hipMemcpyDeviceToHost, b->own));
     HIPCHK(hipStreamSynchronize(b->own));

@@ -77,16 +77,13 @@ extern "C" int mp3d_batch_set_tempo(mp3d_batch *b, int first, int n, const int *
         if (!st_ratio_ok(num[i], den[i])) return MP3D_E_ARG; /* before anything is written */
         t[2 * i] = num[i], t[2 * i + 1] = den[i];
     }
-    HIPCHK(hipSetDevice(b->device));
-    hipStream_t s = b->own;
-    int r = own_after_last(b); /* after the handle's last call, on any stream */
-    if (r) return r;
-    HIPCHK(hipMemcpyAsync(b->sx.tempo + 2 * (size_t)first, t.data(), sizeof(int32_t) * t.size(), hipMemcpyHostToDevice,
-                          s));
-    /* a new tempo is a new stream: the slots' stretch state restarts */
-    HIPCHK(hipMemsetAsync(b->sx.st + first, 0, sizeof(StState) * (size_t)n, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return MP3D_OK;
+    return slots_set(b, [&](hipStream_t s) -> int {
+        HIPCHK(hipMemcpyAsync(b->sx.tempo + 2 * (size_t)first, t.data(), sizeof(int32_t) * t.size(),
+                              hipMemcpyHostToDevice, s));
+        /* a new tempo is a new stream: the slots' stretch state restarts */
+        HIPCHK(hipMemsetAsync(b->sx.st + first, 0, sizeof(StState) * (size_t)n, s));
+        return MP3D_OK;
+    });
 }
 
 /* The stretch stage on stream s: dsmp [n][sstride][channels] samples and dcin

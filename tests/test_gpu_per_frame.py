@@ -15,18 +15,25 @@ import mp3_amd
 pytestmark = pytest.mark.gpu
 
 
-def _decoder(fused, opts=0, readahead=0):
+def _decoder(fused, opts=0, readahead=0, staged=False):
     """readahead=0: every call through the single-frame path under test
-    (the read-ahead has its own tests, tests/test_gpu_readahead.py)"""
-    env = {"MP3D_PF_FUSED": "1" if fused else "0", "MP3D_PF_READAHEAD": str(readahead)}
+    (the read-ahead has its own tests, tests/test_gpu_readahead.py);
+    staged: MP3D_PF_STAGED=1 for the creation only (staged copies instead of
+    mapped buffers), unset otherwise"""
+    env = {"MP3D_PF_FUSED": "1" if fused else "0", "MP3D_PF_READAHEAD": str(readahead),
+           "MP3D_PF_STAGED": "1" if staged else None}
     old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
+    for k, v in env.items():
+        if v is None:
+            os.environ.pop(k, None)
+        else:
+            os.environ[k] = v
     try:
         d = mp3_amd.Decoder()
     finally:
         for k, v in old.items():
             if v is None:
-                del os.environ[k]
+                os.environ.pop(k, None)
             else:
                 os.environ[k] = v
     if opts:
@@ -71,6 +78,24 @@ def test_fused_equals_three_kernel_path_and_golden(name):
 def test_fused_f32(name):
     data, _ = _golden.case(name)
     _same(_frames(_decoder(True), data, f32=True), _frames(_decoder(False), data, f32=True))
+
+
+@pytest.mark.parametrize("f32", [False, True])
+@pytest.mark.parametrize("name", ["keypress_128k_js", "lsf_24k_is"])
+def test_staged_copies_equal_mapped_buffers(name, f32):
+    """MP3D_PF_STAGED: the frame, PCM and info go through staged copies (the
+    batch decode's host-PCM branch that reads the buffer back whole) -- the
+    same frames as the three-kernel path on mapped buffers, mono / LSF rows
+    (half written) included."""
+    data, _ = _golden.case(name)
+    _same(_frames(_decoder(False, staged=True), data, f32=f32), _frames(_decoder(False), data, f32=f32))
+
+
+def test_staged_decoder_has_no_readahead():
+    """a read-ahead needs mapped run buffers: asked for on a staged decoder,
+    every call still decodes its own frame"""
+    data, _ = _golden.case("keypress_128k_js")
+    _same(_frames(_decoder(False, readahead=64, staged=True), data), _frames(_decoder(False), data))
 
 
 def test_fused_crc_option():
