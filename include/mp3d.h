@@ -1096,6 +1096,129 @@ MP3D_API int mp3d_batch_decode_segments(mp3d_batch *b, const uint8_t *frames, co
  * mp3d_batch_set_timing */
 MP3D_API int mp3d_batch_segment_time(mp3d_batch *b, float *us);
 
+/* ---- equaliser sink (biquad cascade) ---------------------------------------- *
+ * Tone control between the decoder and the limiter: a graphic EQ, a rumble
+ * high-pass, a shelf.  In a player's chain: decode -> packed -> EQ -> gain ->
+ * limiter.
+ *
+ * Input signal of a slot: packed-sink output in the handle's format (any of
+ * the nine rates fs, C = out_channels 1 or 2, float32 interleaved): x_c[0 .. N)
+ * since the slot's last equaliser restart.  Sample windows and
+ * MP3D_PACK_GAPLESS act before it.  Samples are finite; a NaN gives an
+ * unspecified result but no fault.
+ *
+ * Curve: one per handle, K = n_bands in [1, MP3D_EQ_MAX_BANDS] second-order
+ * sections, applied to every channel of every stream in the order given.  A
+ * section is designed on the host in long double by the Audio EQ Cookbook
+ * (R. Bristow-Johnson) formulas in their Q form, with w0 = 2 pi f0_hz / fs,
+ * alpha = sin w0 / (2 q), A = 10^(gain_db / 40), cs = cos w0, and for the
+ * shelves sq = 2 sqrt(A) alpha:
+ *   MP3D_EQ_PEAK        b = 1 + alpha A, -2 cs, 1 - alpha A
+ *                       a = 1 + alpha / A, -2 cs, 1 - alpha / A
+ *   MP3D_EQ_LOW_SHELF   b = A ((A+1) - (A-1) cs + sq), 2A ((A-1) - (A+1) cs), A ((A+1) - (A-1) cs - sq)
+ *                       a = (A+1) + (A-1) cs + sq, -2 ((A-1) + (A+1) cs), (A+1) + (A-1) cs - sq
+ *   MP3D_EQ_HIGH_SHELF  b = A ((A+1) + (A-1) cs + sq), -2A ((A-1) + (A+1) cs), A ((A+1) + (A-1) cs - sq)
+ *                       a = (A+1) - (A-1) cs + sq, 2 ((A-1) - (A+1) cs), (A+1) - (A-1) cs - sq
+ *   MP3D_EQ_HIGH_PASS   b = (1 + cs) / 2, -(1 + cs), (1 + cs) / 2;  a = 1 + alpha, -2 cs, 1 - alpha
+ *   MP3D_EQ_LOW_PASS    b = (1 - cs) / 2, 1 - cs, (1 - cs) / 2;     a = 1 + alpha, -2 cs, 1 - alpha
+ * gain_db is not used by the two pass types (it is still range-checked).  With
+ * g = 10^(preamp_db / 20) for stage 1 and g = 1 for the others, a stage's
+ * coefficients are b0 g / a0, b1 g / a0, b2 g / a0, a1 / a0, a2 / a0, each
+ * evaluated in long double in that order and rounded once to double.
+ *
+ * Accepted (else MP3D_E_ARG, nothing changed): type one of the five, f0_hz in
+ * [20, 0.45 fs], q in [0.1, 16], gain_db and preamp_db in [-24, 24].
+ *
+ * Arithmetic, per channel: v = the float32 sample widened to double; each stage
+ * is transposed direct form II in double,
+ *   o = b0 v + s1;  s1 = b1 v - a1 o + s2;  s2 = b2 v - a2 o
+ * stage k + 1 takes stage k's o, and the last stage's o is rounded once to
+ * float32.  It is not clipped: the limiter exists for that.
+ *
+ * Sample counts: the stage emits exactly as many sample frames as it is fed:
+ * no latency, no tail, and a flush emits nothing extra.
+ *
+ * Numerical contract: a tolerance, not bits, for the loudness sink's reason
+ * (the stage runs parallel in time; where a call's tiles fall decides the
+ * order of additions).  The same call on the same state gives the same bits
+ * every time.  With ref the definition above evaluated sequentially in float64
+ * and G the largest |ref| of the stream and channel since its restart, up to
+ * and including the sample,
+ *   |y - ref| <= 2^-22 |ref| + eps G,   eps = 1.32e-10
+ * the first term the float32 rounding of the result (factor 4), eps four times
+ * the largest error over G of a float64 restatement of the time-parallel form
+ * against a long double evaluation (tests/_eq.py).
+ *
+ * The per-slot equaliser state (2 channels x 2 K doubles, 320 bytes reserved)
+ * lives in the handle while the equaliser is set, not in the state blob.  All
+ * zero is a restarted stream.  It restarts where the limiter's does: at
+ * create, at mp3d_batch_reset, at mp3d_batch_set_state on its slot, at
+ * mp3d_batch_set_output (which also turns the equaliser off), at
+ * mp3d_batch_set_eq, at mp3d_batch_set_window on its slot, after its own
+ * MP3D_PACK_FLUSH and after an overflow.                                     */
+#define MP3D_EQ_MAX_BANDS 10
+#define MP3D_EQ_PEAK 0
+#define MP3D_EQ_LOW_SHELF 1
+#define MP3D_EQ_HIGH_SHELF 2
+#define MP3D_EQ_HIGH_PASS 3
+#define MP3D_EQ_LOW_PASS 4
+typedef struct {
+    int type;                 /* MP3D_EQ_*                 */
+    double f0_hz, gain_db, q;
+} mp3d_eq_band;
+
+/* host only: the n_bands sections of a curve at rate hz,
+ * coef[5k .. 5k + 4] = b0 b1 b2 a1 a2 of stage k (a0 = 1).  coef NULL: the
+ * size only.  Returns 5 n_bands.  MP3D_E_ARG for a rate that is not an MPEG
+ * audio rate, cap < 5 n_bands, n_bands outside [1, MP3D_EQ_MAX_BANDS] or any
+ * field outside its range. */
+MP3D_API long long mp3d_eq_design(int hz, const mp3d_eq_band *bands, int n_bands, double preamp_db, double *coef,
+                                  size_t cap);
+
+/* Needs a packed format (mp3d_batch_set_output), else MP3D_E_ARG.  n_bands > 0
+ * designs the curve for the format's rate, uploads its coefficients and
+ * transition tables, restarts every slot's equaliser state and waits for the
+ * handle's work; n_bands = 0 turns the equaliser off and frees its buffers.
+ * After MP3D_E_ARG nothing has changed. */
+MP3D_API int mp3d_batch_set_eq(mp3d_batch *b, const mp3d_eq_band *bands, int n_bands, double preamp_db);
+
+/* The stage: feeds counts[s] (clamped to [0, sample_stride]) sample frames
+ * from samples + s * sample_stride * out_channels per stream through the
+ * slots' equaliser state and writes as many float32 sample frames to out + s *
+ * out_stride * out_channels, their count to out_count[s]; a slot whose count
+ * exceeds out_stride gets -1, writes nothing and restarts.  Nothing past
+ * out_count[s] is written.  samples, counts, out and out_count are host or
+ * device memory (a host samples array is read whole; a host out is filled by
+ * one copy per stream); the call is asynchronous when all four are device
+ * memory.  Device samples and out must be aligned to one sample frame, device
+ * counts to their element, else MP3D_E_ARG; both strides are at most 2^31 - 1,
+ * and n_streams * ceil(min(sample_stride, out_stride) / 4096) at most
+ * (2^32 - 1) / 256, the launch's size, else MP3D_E_CAPACITY; out may not
+ * overlap samples (MP3D_E_ARG).  flags: MP3D_PACK_FLUSH only (the slots
+ * restart after the call).  Runs on the device out and out_count of
+ * mp3d_batch_decode_packed (float32), or with n_streams = 1 on the device
+ * output of mp3d_batch_decode_long_packed: the tiles are independent but for a
+ * small carry, so one long stream is spread over the whole GPU.  Its float32
+ * device out and out_count are valid inputs to every other stage.  Leaves
+ * decoder, resampler and every other sink's state untouched.  MP3D_E_ARG
+ * before mp3d_batch_set_eq. */
+MP3D_API int mp3d_batch_eq(mp3d_batch *b, const float *samples, long long sample_stride, const int *counts,
+                           int n_streams, float *out, long long out_stride, int *out_count, int flags,
+                           void *hip_stream);
+
+/* mp3d_batch_decode_packed (float32) into a handle-owned buffer of stride
+ * mp3d_packed_max_samples(out_hz, frames_per_stream, 0) with device counts,
+ * then the stage on them.  flags: MP3D_PACK_FLUSH | MP3D_PACK_GAPLESS, both
+ * forwarded (the flush ends the resampler, then the equaliser).             */
+MP3D_API int mp3d_batch_decode_equalized(mp3d_batch *b, const uint8_t *frames, const uint64_t *offsets,
+                                         const uint32_t *sizes, int n_streams, int frames_per_stream, float *out,
+                                         long long out_stride, int *out_count, int flags, mp3d_frame_info *infos,
+                                         void *hip_stream);
+
+/* device-side microseconds of the equaliser stage of the last equaliser call
+ * (mp3d_batch_eq, mp3d_batch_decode_equalized); needs mp3d_batch_set_timing */
+MP3D_API int mp3d_batch_eq_time(mp3d_batch *b, float *us);
+
 /* ---- diagnostics -------------------------------------------------------- */
 MP3D_API const char *mp3d_strerror(int err);
 MP3D_API int mp3d_last_hip_error(void);

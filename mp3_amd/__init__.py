@@ -66,7 +66,8 @@ EXPORTS = ["mp3d_dec_create", "mp3d_dec_create_on", "mp3d_dec_destroy", "mp3d_de
            "mp3d_limiter_max_samples", "mp3d_batch_set_limiter", "mp3d_batch_limit", "mp3d_batch_decode_limited",
            "mp3d_batch_limiter_time", "mp3d_segment_threshold", "mp3d_segment_max", "mp3d_batch_set_segments",
            "mp3d_batch_set_segment_threshold", "mp3d_batch_segments", "mp3d_batch_decode_segments",
-           "mp3d_batch_segment_time"]
+           "mp3d_batch_segment_time", "mp3d_eq_design", "mp3d_batch_set_eq", "mp3d_batch_eq",
+           "mp3d_batch_decode_equalized", "mp3d_batch_eq_time"]
 
 OPT_CRC_CHECK = 1  # MP3D_OPT_CRC_CHECK: drop frames whose CRC-16 mismatches
 LONG_GAPLESS = 1  # MP3D_LONG_GAPLESS: apply the LAME tag's trim inside decode_long_packed
@@ -196,6 +197,13 @@ def _bind(L):
         L.mp3d_batch_segments.argtypes = [vp, vp, ctypes.c_longlong, vp, i, vp, ctypes.c_longlong, vp, i, vp]
         L.mp3d_batch_decode_segments.argtypes = [vp, vp, u64p, u32p, i, i, vp, ctypes.c_longlong, vp, i, vp, vp]
         L.mp3d_batch_segment_time.argtypes = [vp, vp]
+    if hasattr(L, "mp3d_batch_set_eq"):  # (an older build loaded for an A/B lacks the equaliser)
+        L.mp3d_eq_design.argtypes = [i, vp, i, ctypes.c_double, vp, ctypes.c_size_t]
+        L.mp3d_eq_design.restype = ctypes.c_longlong
+        L.mp3d_batch_set_eq.argtypes = [vp, vp, i, ctypes.c_double]
+        L.mp3d_batch_eq.argtypes = [vp, vp, ctypes.c_longlong, vp, i, vp, ctypes.c_longlong, vp, i, vp]
+        L.mp3d_batch_decode_equalized.argtypes = [vp, vp, u64p, u32p, i, i, vp, ctypes.c_longlong, vp, i, vp, vp]
+        L.mp3d_batch_eq_time.argtypes = [vp, vp]
     if hasattr(L, "mp3d_debug_wglds_probe"):  # libmp3d_wglds.so only (tests/test_gpu_wglds.py)
         L.mp3d_debug_wglds_probe.argtypes = [i, i, vp, i]
     return L
@@ -434,6 +442,7 @@ class BatchDecoder:
         self._stretch = False  # and the tempo sink
         self._limit = None  # and the limiter (its ceiling in dBTP while it is on)
         self._segments = None  # and the segment sink (its pause and shortest segment in hops while it is on)
+        self._eq = 0  # and the equaliser (its number of bands while it is on)
 
     def decode_packed(self, frames, offsets, sizes, frames_per_stream, out=None, counts=None, infos=None, f32=True,
                       flush=False, stride=None, stream=None, gapless=False):
@@ -926,6 +935,77 @@ class BatchDecoder:
         call (after set_timing)."""
         return self._stage_us(self._L.mp3d_batch_limiter_time)
 
+    def set_eq(self, bands, preamp_db=0.0):
+        """Set the equaliser's curve (mp3d_batch_set_eq): bands a list of up
+        to EQ_MAX_BANDS (type, f0_hz, gain_db, q) with type one of EQ_PEAK,
+        EQ_LOW_SHELF, EQ_HIGH_SHELF, EQ_HIGH_PASS, EQ_LOW_PASS, applied in
+        order to every channel of the packed output; preamp_db scales the
+        whole curve.  None or [] turns the equaliser off.  Needs set_output.
+        Restarts every stream's equaliser state."""
+        arr = _eq_bands(bands)
+        self._ck(self._L.mp3d_batch_set_eq(self._h, arr.ctypes.data if arr.size else None, arr.size,
+                                           float(preamp_db)))
+        self._eq = int(arr.size)
+
+    def _eq_args(self, n, out, out_counts, stride, default_stride):
+        hz, ch = getattr(self, "_out", (0, 0))
+        if stride is None:  # (equaliser off: the call fails with MP3D_E_ARG)
+            stride = int(out.shape[1]) if out is not None else default_stride(hz) if getattr(self, "_eq", 0) else 1
+        stride = int(stride)
+        if out is None:
+            out = np.zeros((n, stride, ch), np.float32)
+        if out_counts is None:
+            out_counts = np.zeros(n, np.int32)
+        return out, out_counts, stride
+
+    def eq(self, samples, counts, out=None, out_counts=None, flush=False, stride=None, stream=None):
+        """The equaliser alone (mp3d_batch_eq): samples float32
+        [n, sample_stride, channels] in the packed format, counts int32 [n]
+        sample frames per stream (both host arrays or device tensors), e.g.
+        the device out and counts of decode_packed.  out: None (allocate host)
+        or float32 array/tensor [n, stride, channels], not overlapping
+        samples; out_counts int32 [n].  stride defaults to out's, else to
+        sample_stride: the stage emits as many samples as it is fed.
+        flush=True restarts the streams after the call.  Returns (out,
+        out_counts): stream s holds out_counts[s] samples per channel (-1:
+        over the stride)."""
+        n, ss = int(samples.shape[0]), int(samples.shape[1])
+        if not hasattr(counts, "data_ptr"):
+            counts = np.ascontiguousarray(counts, np.int32)
+        out, out_counts, stride = self._eq_args(n, out, out_counts, stride, lambda hz: ss)
+        sp, k1 = _ptr(samples)
+        cp, k2 = _ptr(counts)
+        op, k3 = _ptr(out)
+        oc, k4 = _ptr(out_counts)
+        self._ck(self._L.mp3d_batch_eq(self._h, sp if ss else None, ss, cp, n, op, stride, oc, _pack_flags(flush),
+                                       _stream(stream)))
+        return out, out_counts
+
+    def decode_equalized(self, frames, offsets, sizes, frames_per_stream, out=None, counts=None, infos=None,
+                         flush=False, stride=None, stream=None, gapless=False):
+        """Decode as decode_packed does (float32) and write every stream's
+        samples through the equaliser (mp3d_batch_decode_equalized).  stride
+        defaults to out's, else to the bound that cannot overflow.  flush and
+        gapless as in decode_packed; the flush also restarts the equaliser.
+        Returns (out, counts, infos)."""
+        off, sz = self._geom(offsets, sizes)
+        n, F = off.size, int(frames_per_stream)
+        out, counts, stride = self._eq_args(n, out, counts, stride, lambda hz: packed_max_samples(hz, F))
+        if infos is None:
+            infos = np.zeros((n, F), FRAME_INFO_DT)
+        fp, k1 = _ptr(frames)
+        op, k2 = _ptr(out)
+        cp, k3 = _ptr(counts)
+        ip, k4 = _ptr(infos)
+        self._ck(self._L.mp3d_batch_decode_equalized(self._h, fp, off.ctypes.data, sz.ctypes.data, n, F, op, stride, cp,
+                                                     _pack_flags(flush, gapless), ip, _stream(stream)))
+        return out, counts, infos
+
+    def eq_time_us(self):
+        """Device-side microseconds of the equaliser stage of the last
+        equaliser call (after set_timing)."""
+        return self._stage_us(self._L.mp3d_batch_eq_time)
+
     def set_segments(self, on=True, threshold_db=-40.0, min_pause_ms=300, min_speech_ms=100, pad_ms=50):
         """Turn the segment sink on or off (mp3d_batch_set_segments): the
         sample ranges of the packed output, whatever its format, in which the
@@ -1298,6 +1378,32 @@ def stretch_max_samples(hz, in_samples, num=1, den=2):
     """Smallest stride of stretch that can never overflow for one call
     feeding in_samples samples at tempo num / den (mp3d_stretch_max_samples)."""
     return int(_check(lib().mp3d_stretch_max_samples(int(hz), int(in_samples), int(num), int(den))))
+
+
+EQ_MAX_BANDS = 10  # MP3D_EQ_MAX_BANDS
+EQ_PEAK, EQ_LOW_SHELF, EQ_HIGH_SHELF, EQ_HIGH_PASS, EQ_LOW_PASS = range(5)  # MP3D_EQ_*
+EQ_BAND_DT = np.dtype([("type", np.int32), ("f0_hz", np.float64), ("gain_db", np.float64), ("q", np.float64)],
+                      align=True)  # mp3d_eq_band
+
+
+def _eq_bands(bands):
+    """(type, f0_hz, gain_db, q) tuples as an array of mp3d_eq_band"""
+    bands = [] if bands is None else list(bands)
+    arr = np.zeros(len(bands), EQ_BAND_DT)
+    for k, (t, f0, g, q) in enumerate(bands):
+        arr[k] = (int(t), float(f0), float(g), float(q))
+    return arr
+
+
+def eq_design(hz, bands, preamp_db=0.0):
+    """The biquads of an equaliser curve at rate hz (mp3d_eq_design; no GPU
+    needed): float64 [n, 5], row k = b0 b1 b2 a1 a2 of stage k.  bands and
+    preamp_db as in BatchDecoder.set_eq."""
+    arr = _eq_bands(bands)
+    coef = np.zeros((arr.size, 5), np.float64)
+    _check(lib().mp3d_eq_design(int(hz), arr.ctypes.data if arr.size else None, arr.size, float(preamp_db),
+                                coef.ctypes.data, coef.size))
+    return coef
 
 
 def limiter_lookahead(hz):

@@ -2,7 +2,7 @@
  * mp3d_host.h -- private to the host sources (mp3d_host_tables.cpp,
  * mp3d_batch.cpp, mp3d_long.cpp, mp3d_dec.cpp, mp3d_sinks.cpp,
  * mp3d_loudness.cpp, mp3d_normalize.cpp, mp3d_stretch.cpp, mp3d_limiter.cpp,
- * mp3d_segment.cpp):
+ * mp3d_segment.cpp, mp3d_eq.cpp):
  * the error macros, the readers of the environment's knobs, the owning types
  * (DevBuf device memory, PinBuf pinned host memory, Event), the batch handle,
  * the frame that every call shares -- the core decode (DecodeCall,
@@ -36,6 +36,7 @@
 #include "mp3d_stretch.h"
 #include "mp3d_limiter.h"
 #include "mp3d_segment.h"
+#include "mp3d_eq.h"
 #include "mp3d_launch.h"
 
 namespace mp3d {
@@ -405,6 +406,21 @@ struct mp3d_batch {
             on = false, H = P = S = pad = 0;
         }
     } sg;
+    /* equaliser (mp3d_batch_set_eq; mp3d_eq.h): K = 0 is off, and then none of
+     * its buffers exists.  st and plan hold max_streams entries, tab and tpow
+     * the curve's constants; the per-tile scratch tz, entry grows with the
+     * calls. */
+    struct EqSink : Stage {
+        int K = 0; /* sections of the curve */
+        mp3d::DevBuf<EqTab> tab;
+        mp3d::DevBuf<double> tpow, tz, entry;
+        mp3d::DevBuf<EqState> st;
+        mp3d::DevBuf<EqPlan> plan;
+        void off() {
+            Stage::off(), tab.release(), tpow.release(), tz.release(), entry.release(), st.release(), plan.release();
+            K = 0;
+        }
+    } eq;
 };
 
 namespace mp3d {
@@ -465,7 +481,7 @@ inline bool is_device_ptr(const void *p, int device) { return ptr_kind(p, device
  * stage's timer owns its events). */
 /* they read the packed sink's format: off with any change of it */
 inline void stages_off(mp3d_batch *b) {
-    b->ft.off(), b->ld.off(), b->nm.off(), b->ga.off(), b->sx.off(), b->lm.off(), b->sg.off();
+    b->ft.off(), b->ld.off(), b->nm.off(), b->ga.off(), b->sx.off(), b->lm.off(), b->sg.off(), b->eq.off();
 }
 template <class S> hipError_t stage_restart(const DevBuf<S> &st, int first, int n, hipStream_t s) {
     return st ? hipMemsetAsync(st + first, 0, sizeof(S) * (size_t)n, s) : hipSuccess;
@@ -478,6 +494,7 @@ inline int stages_restart(mp3d_batch *b, int first, int n, hipStream_t s) {
     HIPCHK(stage_restart(b->sx.st, first, n, s));
     HIPCHK(stage_restart(b->lm.st, first, n, s));
     HIPCHK(stage_restart(b->sg.st, first, n, s));
+    HIPCHK(stage_restart(b->eq.st, first, n, s));
     return MP3D_OK;
 }
 

@@ -11,7 +11,7 @@
 #include <stdint.h>
 
 /* (layouts: mp3d_internal.h, mp3d_resample.h, mp3d_features.h, mp3d_loudness.h, mp3d_normalize.h,
- * mp3d_stretch.h, mp3d_limiter.h, mp3d_segment.h) */
+ * mp3d_stretch.h, mp3d_limiter.h, mp3d_segment.h, mp3d_eq.h) */
 struct StreamState; struct FrameRec; struct UnitMeta; struct DevTables;
 struct RsState; struct RsCfg; struct RsPlan; struct RsLong;
 struct FtState; struct FtPlan; struct FtTab;
@@ -20,6 +20,7 @@ struct TpState; struct TpPlan;
 struct StState; struct StPlan;
 struct LimState; struct LimPlan;
 struct SgState; struct SgPlan;
+struct EqState; struct EqPlan; struct EqTab;
 
 namespace mp3d {
 
@@ -133,6 +134,13 @@ void launch_segments(const float *samples, const int32_t *counts, SgState *st, S
                      uint64_t *part, uint64_t *bits, long long *seg, int32_t *seg_count, int ch, int n,
                      long long sample_stride, long long seg_stride, int tiles, int H, int P, int S, int pad, int flush,
                      hipStream_t strm);
+
+/* ---- mp3d_eq.hip ---- */
+/* k_eq_plan + k_eq_local + k_eq_carry + k_eq_apply: packed float32 samples through the handle's biquad cascade to
+ * float32; K sections; tpow holds the cascade's A^(TILE t), tz and entry n * tiles * MP3D_EQ_TSTRIDE doubles each */
+void launch_eq(const float *samples, const int32_t *counts, EqState *st, EqPlan *plan, const EqTab *tab,
+               const double *tpow, double *tz, double *entry, float *out, int32_t *out_count, int K, int ch, int n,
+               long long sample_stride, long long out_stride, int tiles, int flush, hipStream_t strm);
 
 } // namespace mp3d
 
