@@ -11,275 +11,30 @@ The compute path is the HIP library mp3_amd/libmp3d.so; there is no CPU
 fallback.  Importing works without a GPU; creating a decoder does not.
 library(path) selects another build of the library (the tests' debug build
 libmp3d_wglds.so) for the decoders created inside the block.
+
+The ctypes side -- structs, constants, the table of every export's signature
+and the loader -- is mp3_amd/_abi.py; its names are re-exported here.
 """
-import contextlib
 import ctypes
-import os
-import pathlib
 
 import numpy as np
 
-_HERE = pathlib.Path(__file__).resolve().parent
-LIB_PATH = pathlib.Path(os.environ["MP3D_LIB"]) if os.environ.get("MP3D_LIB") else _HERE / "libmp3d.so"
-
-MP3D_E = {0: "ok", -1: "bad argument", -2: "no usable HIP device", -3: "HIP runtime error", -4: "out of memory",
-          -5: "batch exceeds handle capacity", -6: "no complete frame in buffer"}
-
-
-class FrameInfo(ctypes.Structure):
-    _fields_ = [("frame_bytes", ctypes.c_int), ("channels", ctypes.c_int), ("hz", ctypes.c_int),
-                ("layer", ctypes.c_int), ("bitrate_kbps", ctypes.c_int), ("samples", ctypes.c_int)]
+from ._abi import (ABI, EQ_BAND_DT, EQ_HIGH_PASS, EQ_HIGH_SHELF, EQ_LOW_PASS, EQ_LOW_SHELF,  # noqa: F401
+                   EQ_MAX_BANDS, EQ_PEAK, EXPORTS, FEAT_LOG10, FRAME_F32, FRAME_INFO_DT, FRAME_LAST, LIB_PATH,
+                   LONG_GAPLESS, MP3D_FEAT_LOG10, OPT_CRC_CHECK, PACK_FLUSH, PACK_GAPLESS, RATES, WINDOW_NO_END,
+                   FrameInfo, MP3DError, StreamInfo, _bind, _check, _load, _loaded, _pack_flags, _ptr, _stream, lib,
+                   library)
 
 
-class StreamInfo(ctypes.Structure):
-    """mp3d_stream_info: leading Xing/Info tag and FFmpeg-style gapless trim."""
-    _fields_ = [("has_tag", ctypes.c_int), ("has_lame", ctypes.c_int), ("enc_delay", ctypes.c_int),
-                ("enc_padding", ctypes.c_int), ("total_frames", ctypes.c_int), ("skip_samples", ctypes.c_int),
-                ("end_sample", ctypes.c_longlong)]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
-
-
-FRAME_INFO_DT = np.dtype([("frame_bytes", np.int32), ("channels", np.int32), ("hz", np.int32),
-                          ("layer", np.int32), ("bitrate_kbps", np.int32), ("samples", np.int32)])
-
-EXPORTS = ["mp3d_dec_create", "mp3d_dec_create_on", "mp3d_dec_destroy", "mp3d_dec_reset", "mp3d_decode_frame",
-           "mp3d_decode_frame_f32", "mp3d_batch_decode_f32",
-           "mp3d_batch_create", "mp3d_batch_destroy", "mp3d_batch_reset", "mp3d_batch_decode", "mp3d_batch_sync",
-           "mp3d_batch_huffman_only", "mp3d_batch_synth_only", "mp3d_strerror", "mp3d_last_hip_error",
-           "mp3d_abi_version", "mp3d_batch_set_timing", "mp3d_batch_kernel_times", "mp3d_batch_stream_info",
-           "mp3d_dec_stream_info", "mp3d_batch_decode_long",
-           "mp3d_long_plan", "mp3d_batch_set_options", "mp3d_dec_set_options", "mp3d_decode_frame_ex",
-           "mp3d_state_bytes", "mp3d_batch_get_state", "mp3d_batch_set_state", "mp3d_dec_get_state",
-           "mp3d_dec_set_state", "mp3d_resample_filter", "mp3d_batch_set_output", "mp3d_packed_max_samples",
-           "mp3d_batch_decode_packed", "mp3d_batch_resample_time", "mp3d_batch_decode_long_packed",
-           "mp3d_long_packed_bound", "mp3d_mel_filterbank", "mp3d_feat_max_frames", "mp3d_batch_set_features",
-           "mp3d_batch_decode_features", "mp3d_batch_features", "mp3d_batch_feature_time", "mp3d_batch_set_window",
-           "mp3d_batch_sink_window", "mp3d_loudness_filter", "mp3d_loud_max_blocks", "mp3d_batch_set_loudness",
-           "mp3d_batch_loudness", "mp3d_batch_decode_loudness", "mp3d_loudness_integrated",
-           "mp3d_batch_loudness_integrated", "mp3d_batch_loudness_time", "mp3d_truepeak_filter",
-           "mp3d_batch_set_true_peak", "mp3d_batch_true_peak", "mp3d_batch_decode_measure",
-           "mp3d_batch_normalize_gain", "mp3d_batch_apply_gain", "mp3d_batch_true_peak_time", "mp3d_stretch_window",
-           "mp3d_stretch_max_samples", "mp3d_batch_set_stretch", "mp3d_batch_set_tempo", "mp3d_batch_stretch",
-           "mp3d_batch_decode_stretched", "mp3d_batch_stretch_time", "mp3d_limiter_lookahead",
-           "mp3d_limiter_max_samples", "mp3d_batch_set_limiter", "mp3d_batch_limit", "mp3d_batch_decode_limited",
-           "mp3d_batch_limiter_time", "mp3d_segment_threshold", "mp3d_segment_max", "mp3d_batch_set_segments",
-           "mp3d_batch_set_segment_threshold", "mp3d_batch_segments", "mp3d_batch_decode_segments",
-           "mp3d_batch_segment_time", "mp3d_eq_design", "mp3d_batch_set_eq", "mp3d_batch_eq",
-           "mp3d_batch_decode_equalized", "mp3d_batch_eq_time"]
-
-OPT_CRC_CHECK = 1  # MP3D_OPT_CRC_CHECK: drop frames whose CRC-16 mismatches
-LONG_GAPLESS = 1  # MP3D_LONG_GAPLESS: apply the LAME tag's trim inside decode_long_packed
-PACK_FLUSH = 1  # MP3D_PACK_FLUSH: feed zeros after the call's frames, then restart the resamplers
-PACK_GAPLESS = 2  # MP3D_PACK_GAPLESS: fix an unfixed sample window from the stream's LAME tag (decode_packed/_features)
-WINDOW_NO_END = 2**63 - 1  # MP3D_WINDOW_NO_END: a sample window without an end
-FEAT_LOG10 = 1  # MP3D_FEAT_LOG10: log10(max(mel, 1e-10)) instead of the mel energies
-MP3D_FEAT_LOG10 = FEAT_LOG10
-RATES = (8000, 11025, 12000, 16000, 22050, 24000, 32000, 44100, 48000)
-FRAME_F32, FRAME_LAST = 1, 2  # mp3d_decode_frame_ex flags
-
-_lib = None
-
-
-class MP3DError(RuntimeError):
-    pass
-
-
-def _bind(L):
-    """Argument and result types of every export, on one loaded build."""
-    vp, i, u64p, u32p = ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p
-    L.mp3d_dec_create.argtypes = [ctypes.POINTER(vp)]
-    L.mp3d_dec_create_on.argtypes = [i, ctypes.POINTER(vp)]
-    L.mp3d_dec_destroy.argtypes = [vp]
-    L.mp3d_dec_destroy.restype = None
-    L.mp3d_dec_reset.argtypes = [vp]
-    L.mp3d_dec_reset.restype = None
-    L.mp3d_decode_frame.argtypes = [vp, ctypes.c_char_p, ctypes.c_size_t, vp, ctypes.POINTER(FrameInfo)]
-    L.mp3d_batch_create.argtypes = [i, i, i, ctypes.POINTER(vp)]
-    L.mp3d_batch_destroy.argtypes = [vp]
-    L.mp3d_batch_destroy.restype = None
-    L.mp3d_batch_reset.argtypes = [vp]
-    L.mp3d_batch_decode.argtypes = [vp, vp, u64p, u32p, i, i, vp, vp, vp]
-    L.mp3d_batch_decode_f32.argtypes = [vp, vp, u64p, u32p, i, i, vp, vp, vp]
-    L.mp3d_decode_frame_f32.argtypes = [vp, ctypes.c_char_p, ctypes.c_size_t, vp, ctypes.POINTER(FrameInfo)]
-    L.mp3d_batch_sync.argtypes = [vp]
-    L.mp3d_batch_huffman_only.argtypes = [vp, vp, u64p, u32p, i, i, vp, vp, vp]
-    L.mp3d_batch_synth_only.argtypes = [vp, vp, vp, vp, i, i, i, i, vp, vp]
-    L.mp3d_strerror.argtypes = [i]
-    L.mp3d_strerror.restype = ctypes.c_char_p
-    L.mp3d_batch_set_timing.argtypes = [vp, i]
-    L.mp3d_batch_kernel_times.argtypes = [vp, vp]
-    L.mp3d_batch_stream_info.argtypes = [vp, i, vp]
-    L.mp3d_dec_stream_info.argtypes = [vp, ctypes.POINTER(StreamInfo)]
-    L.mp3d_batch_decode_long.argtypes = [vp, vp, ctypes.c_size_t, i, vp, i, ctypes.c_longlong, vp,
-                                         ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(StreamInfo)]
-    L.mp3d_long_plan.argtypes = [ctypes.c_char_p, ctypes.c_size_t, i, ctypes.c_longlong, vp, vp,
-                                 ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_int)]
-    L.mp3d_batch_set_options.argtypes = [vp, i]
-    L.mp3d_dec_set_options.argtypes = [vp, i]
-    L.mp3d_decode_frame_ex.argtypes = [vp, ctypes.c_char_p, ctypes.c_size_t, vp, i, ctypes.POINTER(FrameInfo)]
-    L.mp3d_state_bytes.restype = ctypes.c_size_t
-    L.mp3d_batch_get_state.argtypes = [vp, i, i, vp]
-    L.mp3d_batch_set_state.argtypes = [vp, i, i, vp]
-    L.mp3d_dec_get_state.argtypes = [vp, vp]
-    L.mp3d_dec_set_state.argtypes = [vp, vp]
-    ip = ctypes.POINTER(ctypes.c_int)
-    L.mp3d_resample_filter.argtypes = [i, i, ip, ip, ip, vp, ctypes.c_size_t]
-    L.mp3d_resample_filter.restype = ctypes.c_longlong
-    L.mp3d_batch_set_output.argtypes = [vp, i, i]
-    L.mp3d_packed_max_samples.argtypes = [i, i, i]
-    L.mp3d_packed_max_samples.restype = ctypes.c_longlong
-    L.mp3d_batch_decode_packed.argtypes = [vp, vp, u64p, u32p, i, i, vp, i, ctypes.c_longlong, vp, i, vp, vp]
-    L.mp3d_batch_resample_time.argtypes = [vp, vp]
-    L.mp3d_batch_decode_long_packed.argtypes = [vp, vp, ctypes.c_size_t, i, i, i, vp, i, ctypes.c_longlong,
-                                                ctypes.POINTER(ctypes.c_longlong), i, ctypes.POINTER(StreamInfo), ip]
-    L.mp3d_long_packed_bound.argtypes = [ctypes.c_char_p, ctypes.c_size_t, i]
-    L.mp3d_long_packed_bound.restype = ctypes.c_longlong
-    L.mp3d_mel_filterbank.argtypes = [i, vp, ctypes.c_size_t]
-    L.mp3d_mel_filterbank.restype = ctypes.c_longlong
-    L.mp3d_feat_max_frames.argtypes = [i, i]
-    L.mp3d_feat_max_frames.restype = ctypes.c_longlong
-    L.mp3d_batch_set_features.argtypes = [vp, i, i]
-    L.mp3d_batch_decode_features.argtypes = [vp, vp, u64p, u32p, i, i, vp, ctypes.c_longlong, vp, i, vp, vp]
-    L.mp3d_batch_features.argtypes = [vp, vp, ctypes.c_longlong, vp, i, vp, ctypes.c_longlong, vp, i, vp]
-    L.mp3d_batch_feature_time.argtypes = [vp, vp]
-    if hasattr(L, "mp3d_batch_set_window"):  # (an older build loaded for an A/B lacks the two)
-        L.mp3d_batch_set_window.argtypes = [vp, i, i, vp, vp]
-        L.mp3d_batch_sink_window.argtypes = [vp, i, i, vp, vp, vp]
-    if hasattr(L, "mp3d_batch_set_loudness"):  # (an older build loaded for an A/B lacks the loudness sink)
-        L.mp3d_loudness_filter.argtypes = [i, vp, ctypes.c_size_t]
-        L.mp3d_loudness_filter.restype = ctypes.c_longlong
-        L.mp3d_loud_max_blocks.argtypes = [i, i, i]
-        L.mp3d_loud_max_blocks.restype = ctypes.c_longlong
-        L.mp3d_batch_set_loudness.argtypes = [vp, i]
-        L.mp3d_batch_loudness.argtypes = [vp, vp, ctypes.c_longlong, vp, i, vp, ctypes.c_longlong, vp, vp, i, vp]
-        L.mp3d_batch_decode_loudness.argtypes = [vp, vp, u64p, u32p, i, i, vp, ctypes.c_longlong, vp, vp, i, vp, vp]
-        L.mp3d_loudness_integrated.argtypes = [vp, ctypes.c_longlong, ctypes.POINTER(ctypes.c_double)]
-        L.mp3d_batch_loudness_integrated.argtypes = [vp, vp, ctypes.c_longlong, vp, i, vp, vp]
-        L.mp3d_batch_loudness_time.argtypes = [vp, vp]
-    if hasattr(L, "mp3d_batch_set_true_peak"):  # (an older build loaded for an A/B lacks true peak and gain)
-        L.mp3d_truepeak_filter.argtypes = [vp, ctypes.c_size_t]
-        L.mp3d_truepeak_filter.restype = ctypes.c_longlong
-        L.mp3d_batch_set_true_peak.argtypes = [vp, i]
-        L.mp3d_batch_true_peak.argtypes = [vp, vp, ctypes.c_longlong, vp, i, vp, i, vp]
-        L.mp3d_batch_decode_measure.argtypes = [vp, vp, u64p, u32p, i, i, vp, ctypes.c_longlong, vp, vp, vp, i, vp, vp]
-        L.mp3d_batch_normalize_gain.argtypes = [vp, vp, vp, i, ctypes.c_double, ctypes.c_double, vp, vp]
-        L.mp3d_batch_apply_gain.argtypes = [vp, vp, ctypes.c_longlong, vp, i, vp, vp, i, vp]
-        L.mp3d_batch_true_peak_time.argtypes = [vp, vp]
-    if hasattr(L, "mp3d_batch_set_stretch"):  # (an older build loaded for an A/B lacks the tempo sink)
-        L.mp3d_stretch_window.argtypes = [i, vp, ctypes.c_size_t]
-        L.mp3d_stretch_window.restype = ctypes.c_longlong
-        L.mp3d_stretch_max_samples.argtypes = [i, ctypes.c_longlong, i, i]
-        L.mp3d_stretch_max_samples.restype = ctypes.c_longlong
-        L.mp3d_batch_set_stretch.argtypes = [vp, i]
-        L.mp3d_batch_set_tempo.argtypes = [vp, i, i, vp, vp]
-        L.mp3d_batch_stretch.argtypes = [vp, vp, ctypes.c_longlong, vp, i, vp, ctypes.c_longlong, vp, i, vp]
-        L.mp3d_batch_decode_stretched.argtypes = [vp, vp, u64p, u32p, i, i, vp, ctypes.c_longlong, vp, i, vp, vp]
-        L.mp3d_batch_stretch_time.argtypes = [vp, vp]
-    if hasattr(L, "mp3d_batch_set_limiter"):  # (an older build loaded for an A/B lacks the limiter)
-        L.mp3d_limiter_lookahead.argtypes = [i]
-        L.mp3d_limiter_lookahead.restype = ctypes.c_longlong
-        L.mp3d_limiter_max_samples.argtypes = [i, ctypes.c_longlong]
-        L.mp3d_limiter_max_samples.restype = ctypes.c_longlong
-        L.mp3d_batch_set_limiter.argtypes = [vp, i, ctypes.c_double]
-        L.mp3d_batch_limit.argtypes = [vp, vp, ctypes.c_longlong, vp, i, vp, vp, i, ctypes.c_longlong, vp, vp, i, vp]
-        L.mp3d_batch_decode_limited.argtypes = [vp, vp, u64p, u32p, i, i, vp, vp, i, ctypes.c_longlong, vp, vp, i, vp,
-                                                vp]
-        L.mp3d_batch_limiter_time.argtypes = [vp, vp]
-    if hasattr(L, "mp3d_batch_set_segments"):  # (an older build loaded for an A/B lacks the segment sink)
-        L.mp3d_segment_threshold.argtypes = [i, ctypes.c_double]
-        L.mp3d_segment_threshold.restype = ctypes.c_longlong
-        L.mp3d_segment_max.argtypes = [i, ctypes.c_longlong, i, i]
-        L.mp3d_segment_max.restype = ctypes.c_longlong
-        L.mp3d_batch_set_segments.argtypes = [vp, i, i, i, i]
-        L.mp3d_batch_set_segment_threshold.argtypes = [vp, i, i, vp]
-        L.mp3d_batch_segments.argtypes = [vp, vp, ctypes.c_longlong, vp, i, vp, ctypes.c_longlong, vp, i, vp]
-        L.mp3d_batch_decode_segments.argtypes = [vp, vp, u64p, u32p, i, i, vp, ctypes.c_longlong, vp, i, vp, vp]
-        L.mp3d_batch_segment_time.argtypes = [vp, vp]
-    if hasattr(L, "mp3d_batch_set_eq"):  # (an older build loaded for an A/B lacks the equaliser)
-        L.mp3d_eq_design.argtypes = [i, vp, i, ctypes.c_double, vp, ctypes.c_size_t]
-        L.mp3d_eq_design.restype = ctypes.c_longlong
-        L.mp3d_batch_set_eq.argtypes = [vp, vp, i, ctypes.c_double]
-        L.mp3d_batch_eq.argtypes = [vp, vp, ctypes.c_longlong, vp, i, vp, ctypes.c_longlong, vp, i, vp]
-        L.mp3d_batch_decode_equalized.argtypes = [vp, vp, u64p, u32p, i, i, vp, ctypes.c_longlong, vp, i, vp, vp]
-        L.mp3d_batch_eq_time.argtypes = [vp, vp]
-    if hasattr(L, "mp3d_debug_wglds_probe"):  # libmp3d_wglds.so only (tests/test_gpu_wglds.py)
-        L.mp3d_debug_wglds_probe.argtypes = [i, i, vp, i]
-    return L
-
-
-_loaded = {}  # path -> CDLL: one copy of a build per process
-
-
-def _load(path):
-    path = pathlib.Path(path).resolve()
-    if path not in _loaded:
-        if not path.exists():
-            raise ImportError("mp3_amd: %s missing -- run __graft_entry__.build() (no CPU fallback exists)" % path)
-        _loaded[path] = _bind(ctypes.CDLL(str(path)))
-    return _loaded[path]
-
-
-def lib():
-    """The current build of the library: libmp3d.so (or MP3D_LIB) unless
-    inside library().  Fails loudly if it was not built."""
-    global _lib
-    if _lib is None:
-        _lib = _load(LIB_PATH)
-    return _lib
-
-
-@contextlib.contextmanager
-def library(path):
-    """Make lib() return the build at `path` inside the block (a debug build
-    next to the product in one process).  A Decoder / BatchDecoder keeps the
-    build that created its handle for every later call, whatever is current
-    then; the module-level functions use the current one."""
-    global _lib
-    prev, _lib = _lib, _load(path)
-    try:
-        yield _lib
-    finally:
-        _lib = prev
-
-
-def _check(rc, L=None):
-    if rc < 0:
-        L = L or lib()
-        raise MP3DError("mp3d error %d (%s), hip error %d" % (rc, L.mp3d_strerror(rc).decode(), L.mp3d_last_hip_error()))
-    return rc
-
-
-def _ptr(x):
-    """(pointer, keepalive) for a numpy array, torch tensor, bytes or None."""
-    if x is None:
-        return None, None
-    if isinstance(x, (bytes, bytearray)):
-        a = np.frombuffer(bytes(x), np.uint8)
-        return a.ctypes.data, a
-    if isinstance(x, np.ndarray):
-        if not x.flags.c_contiguous:
-            raise ValueError("array must be C-contiguous")
-        return x.ctypes.data, x
-    if hasattr(x, "data_ptr"):
-        if not x.is_contiguous():
-            raise ValueError("tensor must be contiguous")
-        return x.data_ptr(), x
-    raise TypeError("unsupported buffer type %r" % type(x))
-
-
-def _pack_flags(flush, gapless=False):
-    return (PACK_FLUSH if flush else 0) | (PACK_GAPLESS if gapless else 0)
-
-
-def _stream(stream):
-    """A HIP stream handle (int) as a call's hip_stream argument; None / 0: the handle's own stream."""
-    return ctypes.c_void_p(stream) if stream else None
+def _host(x, dtype):
+    """x as it is when None or a device tensor, else a C-contiguous host array of dtype"""
+    return x if x is None or hasattr(x, "data_ptr") else np.ascontiguousarray(x, dtype)
 
 
 class Decoder:
     """Per-frame decoder (mp3d_decode_frame), one per stream."""
+
+    _h = None  # (no handle yet: close() after a failed create has nothing to destroy)
 
     def __init__(self, device=None):
         L = self._L = lib()  # the build that owns the handle: every later call goes to it
@@ -294,7 +49,7 @@ class Decoder:
         return _check(rc, self._L)
 
     def close(self):
-        if getattr(self, "_h", None):
+        if self._h:
             self._L.mp3d_dec_destroy(self._h)
             self._h = None
 
@@ -364,6 +119,18 @@ class Decoder:
 class BatchDecoder:
     """Batched decoder: per-stream state stays in HBM across calls."""
 
+    _h = None  # (no handle yet: close() after a failed create has nothing to destroy)
+    # What the wrapper knows of the handle's sinks, as the handle starts out.
+    _out = (0, 0)  # the packed format (hz, channels); hz = 0: off
+    _mels = 0  # feature sink: its number of mel filters
+    _loud = False  # loudness sink
+    _tp = False  # true-peak tap
+    _stretch = False  # tempo sink
+    _limit = None  # limiter: its ceiling in dBTP while it is on
+    _segments = None  # segment sink: its pause and shortest segment in hops while it is on
+    _eq = 0  # equaliser: its number of bands
+    _AFTER_PACKED = ("_mels", "_loud", "_tp", "_stretch", "_limit", "_segments", "_eq")
+
     def __init__(self, max_streams, max_frames, device=0):
         L = self._L = lib()  # the build that owns the handle: every later call goes to it
         h = ctypes.c_void_p()
@@ -381,7 +148,7 @@ class BatchDecoder:
         return float(t.value)
 
     def close(self):
-        if getattr(self, "_h", None):
+        if self._h:
             self._L.mp3d_batch_destroy(self._h)
             self._h = None
 
@@ -413,21 +180,54 @@ class BatchDecoder:
             raise ValueError("offsets/sizes shape mismatch")
         return off, sz
 
+    def _decode_head(self, frames, offsets, sizes, frames_per_stream, infos=None):
+        """The start of every decode call: (head, n, F, infos, keep) with head
+        the leading C arguments (handle, frames, offsets, sizes, n_streams,
+        frames_per_stream), infos the caller's or a host array [n, F], and
+        keep what head points into, to hold until the call has returned."""
+        off, sz = self._geom(offsets, sizes)
+        n, F = off.size, int(frames_per_stream)
+        if infos is None:
+            infos = np.zeros((n, F), FRAME_INFO_DT)
+        fp, keep = _ptr(frames)
+        return (self._h, fp, off.ctypes.data, sz.ctypes.data, n, F), n, F, infos, (keep, off, sz)
+
+    @staticmethod
+    def _stage_head(samples, counts, stride=None):
+        """The start of every stage-alone call: (head, n, ss, keep) with head
+        the C arguments after the handle (samples or NULL when there are none,
+        sample_stride, counts, n_streams); samples [n, ss, ...], ss read from
+        stride when given; counts int32 [n], a host sequence or a device
+        tensor; keep as in _decode_head."""
+        n, ss = int(samples.shape[0]), int(samples.shape[1]) if stride is None else int(stride)
+        counts = _host(counts, np.int32)
+        sp, cp = _ptr(samples)[0], _ptr(counts)[0]
+        return (sp if ss else None, ss, cp, n), n, ss, counts
+
+    @staticmethod
+    def _sink_out(n, out, counts, stride, on, bound, tail, dtype):
+        """The output of every sink call: (out, counts, stride).  The stride
+        is out's, else bound() if the sink is on, else 1 (the call then fails
+        with MP3D_E_ARG); out [n, stride, *tail] of dtype and counts int32 [n]
+        are host arrays unless given."""
+        if stride is None:
+            stride = int(out.shape[1]) if out is not None else bound() if on else 1
+        stride = int(stride)
+        if out is None:
+            out = np.zeros((n, stride) + tuple(tail), dtype)
+        if counts is None:
+            counts = np.zeros(n, np.int32)
+        return out, counts, stride
+
     def decode(self, frames, offsets, sizes, frames_per_stream, pcm=None, infos=None, stream=None, f32=False):
         """frames: bytes/np.uint8/torch.uint8; pcm: None (allocate host) or
         int16 (float32 with f32=True) array/tensor [n, F, 2304]; infos: None
         or FRAME_INFO_DT array / int32 tensor [n, F, 6].  Returns (pcm, infos)."""
-        off, sz = self._geom(offsets, sizes)
-        n, F = off.size, int(frames_per_stream)
+        head, n, F, infos, keep = self._decode_head(frames, offsets, sizes, frames_per_stream, infos)
         if pcm is None:
             pcm = np.zeros((n, F, 2304), np.float32 if f32 else np.int16)
-        if infos is None:
-            infos = np.zeros((n, F), FRAME_INFO_DT)
-        fp, k1 = _ptr(frames)
-        pp, k2 = _ptr(pcm)
-        ip, k3 = _ptr(infos)
         fn = self._L.mp3d_batch_decode_f32 if f32 else self._L.mp3d_batch_decode
-        self._ck(fn(self._h, fp, off.ctypes.data, sz.ctypes.data, n, F, pp, ip, _stream(stream)))
+        self._ck(fn(*head, _ptr(pcm)[0], _ptr(infos)[0], _stream(stream)))
         return pcm, infos
 
     def set_output(self, hz, channels):
@@ -436,13 +236,8 @@ class BatchDecoder:
         restarts every stream's resampler."""
         self._ck(self._L.mp3d_batch_set_output(self._h, int(hz), int(channels)))
         self._out = (int(hz), int(channels))
-        self._mels = 0  # a change of the output format turns the feature sink off
-        self._loud = False  # and the loudness sink
-        self._tp = False  # and the true-peak tap
-        self._stretch = False  # and the tempo sink
-        self._limit = None  # and the limiter (its ceiling in dBTP while it is on)
-        self._segments = None  # and the segment sink (its pause and shortest segment in hops while it is on)
-        self._eq = 0  # and the equaliser (its number of bands while it is on)
+        for name in self._AFTER_PACKED:  # a change of the output format turns every sink after the packed one off
+            setattr(self, name, getattr(BatchDecoder, name))
 
     def decode_packed(self, frames, offsets, sizes, frames_per_stream, out=None, counts=None, infos=None, f32=True,
                       flush=False, stride=None, stream=None, gapless=False):
@@ -456,25 +251,12 @@ class BatchDecoder:
         every stream that has none yet from its LAME tag (set_window).  Returns
         (out, counts, infos); stream s holds counts[s] samples per channel
         (-1: over the stride)."""
-        off, sz = self._geom(offsets, sizes)
-        n, F = off.size, int(frames_per_stream)
-        hz, ch = getattr(self, "_out", (0, 0))
-        if stride is None:  # (no format set: the call below fails with MP3D_E_ARG)
-            stride = int(out.shape[1]) if out is not None else packed_max_samples(hz, F) if hz else 1
-        stride = int(stride)
-        if out is None:
-            out = np.zeros((n, stride, ch), np.float32 if f32 else np.int16)
-        if counts is None:
-            counts = np.zeros(n, np.int32)
-        if infos is None:
-            infos = np.zeros((n, F), FRAME_INFO_DT)
-        fp, k1 = _ptr(frames)
-        op, k2 = _ptr(out)
-        cp, k3 = _ptr(counts)
-        ip, k4 = _ptr(infos)
-        self._ck(self._L.mp3d_batch_decode_packed(self._h, fp, off.ctypes.data, sz.ctypes.data, n, F, op, int(bool(f32)),
-                                              stride, cp,
-                                              _pack_flags(flush, gapless), ip, _stream(stream)))
+        head, n, F, infos, keep = self._decode_head(frames, offsets, sizes, frames_per_stream, infos)
+        hz, ch = self._out
+        out, counts, stride = self._sink_out(n, out, counts, stride, hz, lambda: packed_max_samples(hz, F), (ch,),
+                                             np.float32 if f32 else np.int16)
+        self._ck(self._L.mp3d_batch_decode_packed(*head, _ptr(out)[0], int(bool(f32)), stride, _ptr(counts)[0],
+                                                  _pack_flags(flush, gapless), _ptr(infos)[0], _stream(stream)))
         return out, counts, infos
 
     def set_window(self, lo, hi=None, first=0):
@@ -530,17 +312,6 @@ class BatchDecoder:
         self._ck(self._L.mp3d_batch_set_features(self._h, int(n_mels), FEAT_LOG10 if log10 else 0))
         self._mels = int(n_mels)
 
-    def _feat_args(self, n, feat, counts, stride, default_stride):
-        nm = getattr(self, "_mels", 0)
-        if stride is None:  # (features off: the call fails with MP3D_E_ARG)
-            stride = int(feat.shape[1]) if feat is not None else default_stride() if nm else 1
-        stride = int(stride)
-        if feat is None:
-            feat = np.zeros((n, stride, max(nm, 1)), np.float32)
-        if counts is None:
-            counts = np.zeros(n, np.int32)
-        return feat, counts, stride
-
     def decode_features(self, frames, offsets, sizes, frames_per_stream, feat=None, counts=None, infos=None,
                         flush=False, stride=None, stream=None, gapless=False):
         """Decode as decode_packed does and write every stream's log-mel
@@ -551,17 +322,11 @@ class BatchDecoder:
         feature tails are emitted and both restart.  gapless as in
         decode_packed.  Returns (feat, counts, infos); stream s holds
         counts[s] frames (-1: over the stride)."""
-        off, sz = self._geom(offsets, sizes)
-        n, F = off.size, int(frames_per_stream)
-        feat, counts, stride = self._feat_args(n, feat, counts, stride, lambda: feat_max_frames(F))
-        if infos is None:
-            infos = np.zeros((n, F), FRAME_INFO_DT)
-        fp, k1 = _ptr(frames)
-        op, k2 = _ptr(feat)
-        cp, k3 = _ptr(counts)
-        ip, k4 = _ptr(infos)
-        self._ck(self._L.mp3d_batch_decode_features(self._h, fp, off.ctypes.data, sz.ctypes.data, n, F, op, stride, cp,
-                                                    _pack_flags(flush, gapless), ip, _stream(stream)))
+        head, n, F, infos, keep = self._decode_head(frames, offsets, sizes, frames_per_stream, infos)
+        feat, counts, stride = self._sink_out(n, feat, counts, stride, self._mels, lambda: feat_max_frames(F),
+                                              (max(self._mels, 1),), np.float32)
+        self._ck(self._L.mp3d_batch_decode_features(*head, _ptr(feat)[0], stride, _ptr(counts)[0],
+                                                    _pack_flags(flush, gapless), _ptr(infos)[0], _stream(stream)))
         return feat, counts, infos
 
     def features(self, samples, counts, feat=None, feat_counts=None, flush=False, stride=None, stream=None):
@@ -569,15 +334,11 @@ class BatchDecoder:
         [n, sample_stride] 16 kHz mono, counts int32 [n] samples per stream
         (both host arrays or device tensors), through the same kernels and
         per-stream state as decode_features.  Returns (feat, feat_counts)."""
-        n, ss = int(samples.shape[0]), int(samples.shape[1])
-        if not hasattr(counts, "data_ptr"):
-            counts = np.ascontiguousarray(counts, np.int32)
-        feat, feat_counts, stride = self._feat_args(n, feat, feat_counts, stride, lambda: (ss + 200 + 159) // 160 + 1)
-        sp, k1 = _ptr(samples)
-        cp, k2 = _ptr(counts)
-        op, k3 = _ptr(feat)
-        fc, k4 = _ptr(feat_counts)
-        self._ck(self._L.mp3d_batch_features(self._h, sp if ss else None, ss, cp, n, op, stride, fc,
+        head, n, ss, keep = self._stage_head(samples, counts)
+        feat, feat_counts, stride = self._sink_out(n, feat, feat_counts, stride, self._mels,
+                                                   lambda: (ss + 200 + 159) // 160 + 1, (max(self._mels, 1),),
+                                                   np.float32)
+        self._ck(self._L.mp3d_batch_features(self._h, *head, _ptr(feat)[0], stride, _ptr(feat_counts)[0],
                                              _pack_flags(flush), _stream(stream)))
         return feat, feat_counts
 
@@ -594,18 +355,6 @@ class BatchDecoder:
         self._ck(self._L.mp3d_batch_set_loudness(self._h, int(bool(on))))
         self._loud = bool(on)
 
-    def _loud_args(self, n, blocks, counts, peak, stride, default_stride):
-        if stride is None:  # (loudness off: the call fails with MP3D_E_ARG)
-            stride = int(blocks.shape[1]) if blocks is not None else default_stride() if getattr(self, "_loud", 0) else 1
-        stride = int(stride)
-        if blocks is None:
-            blocks = np.zeros((n, stride), np.float32)
-        if counts is None:
-            counts = np.zeros(n, np.int32)
-        if peak is None:
-            peak = np.zeros(n, np.float32)
-        return blocks, counts, peak, stride
-
     def loudness(self, samples, counts, blocks=None, block_counts=None, peak=None, flush=False, stride=None,
                  stream=None):
         """The loudness stage alone (mp3d_batch_loudness): samples float32
@@ -616,19 +365,13 @@ class BatchDecoder:
         float32 [n].  flush=True drops the open block and restarts the streams.
         Returns (blocks, block_counts, peak): stream s holds block_counts[s]
         block energies (-1: over the stride)."""
-        n, ss = int(samples.shape[0]), int(samples.shape[1])
-        if not hasattr(counts, "data_ptr"):
-            counts = np.ascontiguousarray(counts, np.int32)
-        H = (getattr(self, "_out", (0, 0))[0] + 5) // 10
-        blocks, block_counts, peak, stride = self._loud_args(n, blocks, block_counts, peak, stride,
-                                                             lambda: (H - 1 + ss) // H)
-        sp, k1 = _ptr(samples)
-        cp, k2 = _ptr(counts)
-        op, k3 = _ptr(blocks)
-        bc, k4 = _ptr(block_counts)
-        pp, k5 = _ptr(peak)
-        self._ck(self._L.mp3d_batch_loudness(self._h, sp if ss else None, ss, cp, n, op, stride, bc, pp,
-                                             _pack_flags(flush), _stream(stream)))
+        head, n, ss, keep = self._stage_head(samples, counts)
+        H = (self._out[0] + 5) // 10
+        blocks, block_counts, stride = self._sink_out(n, blocks, block_counts, stride, self._loud,
+                                                      lambda: (H - 1 + ss) // H, (), np.float32)
+        peak = np.zeros(n, np.float32) if peak is None else peak
+        self._ck(self._L.mp3d_batch_loudness(self._h, *head, _ptr(blocks)[0], stride, _ptr(block_counts)[0],
+                                             _ptr(peak)[0], _pack_flags(flush), _stream(stream)))
         return blocks, block_counts, peak
 
     def decode_loudness(self, frames, offsets, sizes, frames_per_stream, blocks=None, counts=None, peak=None,
@@ -638,19 +381,12 @@ class BatchDecoder:
         defaults to blocks', else to loud_max_blocks.  flush and gapless as in
         decode_packed; the flush also drops the open block.  Returns (blocks,
         counts, peak, infos)."""
-        off, sz = self._geom(offsets, sizes)
-        n, F = off.size, int(frames_per_stream)
-        hz = getattr(self, "_out", (0, 0))[0]
-        blocks, counts, peak, stride = self._loud_args(n, blocks, counts, peak, stride, lambda: loud_max_blocks(hz, F))
-        if infos is None:
-            infos = np.zeros((n, F), FRAME_INFO_DT)
-        fp, k1 = _ptr(frames)
-        op, k2 = _ptr(blocks)
-        cp, k3 = _ptr(counts)
-        pp, k4 = _ptr(peak)
-        ip, k5 = _ptr(infos)
-        self._ck(self._L.mp3d_batch_decode_loudness(self._h, fp, off.ctypes.data, sz.ctypes.data, n, F, op, stride, cp, pp,
-                                                    _pack_flags(flush, gapless), ip, _stream(stream)))
+        head, n, F, infos, keep = self._decode_head(frames, offsets, sizes, frames_per_stream, infos)
+        blocks, counts, stride = self._sink_out(n, blocks, counts, stride, self._loud,
+                                                lambda: loud_max_blocks(self._out[0], F), (), np.float32)
+        peak = np.zeros(n, np.float32) if peak is None else peak
+        self._ck(self._L.mp3d_batch_decode_loudness(*head, _ptr(blocks)[0], stride, _ptr(counts)[0], _ptr(peak)[0],
+                                                    _pack_flags(flush, gapless), _ptr(infos)[0], _stream(stream)))
         return blocks, counts, peak, infos
 
     def integrated_lufs(self, blocks, counts, lufs=None, stream=None):
@@ -658,16 +394,10 @@ class BatchDecoder:
         [n, stride] holding counts[s] block energies, on the GPU
         (mp3d_batch_loudness_integrated); host arrays or device tensors.
         Returns lufs float32 [n], -inf for a row of fewer than 4 blocks."""
-        n, stride = int(blocks.shape[0]), int(blocks.shape[1])
-        if not hasattr(counts, "data_ptr"):
-            counts = np.ascontiguousarray(counts, np.int32)
+        head, n, stride, keep = self._stage_head(blocks, counts)
         if lufs is None:
             lufs = np.zeros(n, np.float32)
-        bp, k1 = _ptr(blocks)
-        cp, k2 = _ptr(counts)
-        lp, k3 = _ptr(lufs)
-        self._ck(self._L.mp3d_batch_loudness_integrated(self._h, bp if stride else None, stride, cp, n, lp,
-                                                        _stream(stream)))
+        self._ck(self._L.mp3d_batch_loudness_integrated(self._h, *head, _ptr(lufs)[0], _stream(stream)))
         return lufs
 
     def loudness_time_us(self):
@@ -691,16 +421,10 @@ class BatchDecoder:
         float32 array/tensor [n].  flush=True emits the last 6 indices of every
         stream and restarts it.  Returns tpeak; the true peak of a stream fed
         in several calls is the max of theirs."""
-        n, ss = int(samples.shape[0]), int(samples.shape[1]) if stride is None else int(stride)
-        if not hasattr(counts, "data_ptr"):
-            counts = np.ascontiguousarray(counts, np.int32)
+        head, n, ss, keep = self._stage_head(samples, counts, stride)
         if tpeak is None:
             tpeak = np.zeros(n, np.float32)
-        sp, k1 = _ptr(samples)
-        cp, k2 = _ptr(counts)
-        tp, k3 = _ptr(tpeak)
-        self._ck(self._L.mp3d_batch_true_peak(self._h, sp if ss else None, ss, cp, n, tp, _pack_flags(flush),
-                                              _stream(stream)))
+        self._ck(self._L.mp3d_batch_true_peak(self._h, *head, _ptr(tpeak)[0], _pack_flags(flush), _stream(stream)))
         return tpeak
 
     def decode_measure(self, frames, offsets, sizes, frames_per_stream, blocks=None, counts=None, peak=None,
@@ -708,22 +432,14 @@ class BatchDecoder:
         """decode_loudness plus the true-peak tap on the same samples
         (mp3d_batch_decode_measure); needs set_loudness and set_true_peak.
         Returns (blocks, counts, peak, tpeak, infos)."""
-        off, sz = self._geom(offsets, sizes)
-        n, F = off.size, int(frames_per_stream)
-        hz = getattr(self, "_out", (0, 0))[0]
-        blocks, counts, peak, stride = self._loud_args(n, blocks, counts, peak, stride, lambda: loud_max_blocks(hz, F))
-        if tpeak is None:
-            tpeak = np.zeros(n, np.float32)
-        if infos is None:
-            infos = np.zeros((n, F), FRAME_INFO_DT)
-        fp, k1 = _ptr(frames)
-        op, k2 = _ptr(blocks)
-        cp, k3 = _ptr(counts)
-        pp, k4 = _ptr(peak)
-        tp, k5 = _ptr(tpeak)
-        ip, k6 = _ptr(infos)
-        self._ck(self._L.mp3d_batch_decode_measure(self._h, fp, off.ctypes.data, sz.ctypes.data, n, F, op, stride, cp, pp,
-                                                   tp, _pack_flags(flush, gapless), ip, _stream(stream)))
+        head, n, F, infos, keep = self._decode_head(frames, offsets, sizes, frames_per_stream, infos)
+        blocks, counts, stride = self._sink_out(n, blocks, counts, stride, self._loud,
+                                                lambda: loud_max_blocks(self._out[0], F), (), np.float32)
+        peak = np.zeros(n, np.float32) if peak is None else peak
+        tpeak = np.zeros(n, np.float32) if tpeak is None else tpeak
+        self._ck(self._L.mp3d_batch_decode_measure(*head, _ptr(blocks)[0], stride, _ptr(counts)[0], _ptr(peak)[0],
+                                                   _ptr(tpeak)[0], _pack_flags(flush, gapless), _ptr(infos)[0],
+                                                   _stream(stream)))
         return blocks, counts, peak, tpeak, infos
 
     def normalize_gain(self, lufs, tpeak=None, target=-23.0, max_dbtp=-1.0, gain=None, stream=None):
@@ -732,18 +448,12 @@ class BatchDecoder:
         (mp3d_batch_normalize_gain); tpeak=None: no limit.  A stream whose
         loudness is not finite gets gain 1.  Host arrays or device tensors,
         float32 [n].  Returns gain."""
-        if not hasattr(lufs, "data_ptr"):
-            lufs = np.ascontiguousarray(lufs, np.float32)
-        if tpeak is not None and not hasattr(tpeak, "data_ptr"):
-            tpeak = np.ascontiguousarray(tpeak, np.float32)
+        lufs, tpeak = _host(lufs, np.float32), _host(tpeak, np.float32)
         n = int(lufs.shape[0])
         if gain is None:
             gain = np.zeros(n, np.float32)
-        lp, k1 = _ptr(lufs)
-        tp, k2 = _ptr(tpeak)
-        gp, k3 = _ptr(gain)
-        self._ck(self._L.mp3d_batch_normalize_gain(self._h, lp, tp, n, float(target), float(max_dbtp), gp,
-                                                   _stream(stream)))
+        self._ck(self._L.mp3d_batch_normalize_gain(self._h, _ptr(lufs)[0], _ptr(tpeak)[0], n, float(target),
+                                                   float(max_dbtp), _ptr(gain)[0], _stream(stream)))
         return gain
 
     def apply_gain(self, samples, counts, gain, out=None, f32=True, stream=None):
@@ -753,18 +463,11 @@ class BatchDecoder:
         host, zeros past the counts) or float32 (int16 with f32=False)
         array/tensor of samples' shape, which may be samples itself for
         float32.  Nothing past counts[s] is written.  Returns out."""
-        n, ss = int(samples.shape[0]), int(samples.shape[1])
-        if not hasattr(counts, "data_ptr"):
-            counts = np.ascontiguousarray(counts, np.int32)
-        if not hasattr(gain, "data_ptr"):
-            gain = np.ascontiguousarray(gain, np.float32)
+        head, n, ss, keep = self._stage_head(samples, counts)
+        gain = _host(gain, np.float32)
         if out is None:
             out = np.zeros(tuple(samples.shape), np.float32 if f32 else np.int16)
-        sp, k1 = _ptr(samples)
-        cp, k2 = _ptr(counts)
-        gp, k3 = _ptr(gain)
-        op, k4 = _ptr(out)
-        self._ck(self._L.mp3d_batch_apply_gain(self._h, sp if ss else None, ss, cp, n, gp, op, int(bool(f32)),
+        self._ck(self._L.mp3d_batch_apply_gain(self._h, *head, _ptr(gain)[0], _ptr(out)[0], int(bool(f32)),
                                                _stream(stream)))
         return out
 
@@ -792,17 +495,6 @@ class BatchDecoder:
             raise ValueError("num / den length mismatch")
         self._ck(self._L.mp3d_batch_set_tempo(self._h, int(first), num.size, num.ctypes.data, den.ctypes.data))
 
-    def _stretch_args(self, n, out, out_counts, stride, default_stride):
-        hz, ch = getattr(self, "_out", (0, 0))
-        if stride is None:  # (stretch off: the call fails with MP3D_E_ARG)
-            stride = int(out.shape[1]) if out is not None else default_stride(hz) if getattr(self, "_stretch", 0) else 1
-        stride = int(stride)
-        if out is None:
-            out = np.zeros((n, stride, ch), np.float32)
-        if out_counts is None:
-            out_counts = np.zeros(n, np.int32)
-        return out, out_counts, stride
-
     def stretch(self, samples, counts, out=None, out_counts=None, flush=False, stride=None, stream=None):
         """The tempo sink alone (mp3d_batch_stretch): samples float32
         [n, sample_stride, channels] in the packed format, counts int32 [n]
@@ -813,16 +505,11 @@ class BatchDecoder:
         that cannot overflow at the slowest tempo.  flush=True emits the rest
         of every stream and restarts it.  Returns (out, out_counts): stream s
         holds out_counts[s] samples per channel (-1: over the stride)."""
-        n, ss = int(samples.shape[0]), int(samples.shape[1])
-        if not hasattr(counts, "data_ptr"):
-            counts = np.ascontiguousarray(counts, np.int32)
-        out, out_counts, stride = self._stretch_args(n, out, out_counts, stride,
-                                                     lambda hz: stretch_max_samples(hz, ss, 1, 2))
-        sp, k1 = _ptr(samples)
-        cp, k2 = _ptr(counts)
-        op, k3 = _ptr(out)
-        oc, k4 = _ptr(out_counts)
-        self._ck(self._L.mp3d_batch_stretch(self._h, sp if ss else None, ss, cp, n, op, stride, oc,
+        head, n, ss, keep = self._stage_head(samples, counts)
+        hz, ch = self._out
+        out, out_counts, stride = self._sink_out(n, out, out_counts, stride, self._stretch,
+                                                 lambda: stretch_max_samples(hz, ss, 1, 2), (ch,), np.float32)
+        self._ck(self._L.mp3d_batch_stretch(self._h, *head, _ptr(out)[0], stride, _ptr(out_counts)[0],
                                             _pack_flags(flush), _stream(stream)))
         return out, out_counts
 
@@ -833,18 +520,13 @@ class BatchDecoder:
         out's, else to the bound that cannot overflow at the slowest tempo.
         flush and gapless as in decode_packed; the flush also ends the
         stretch.  Returns (out, counts, infos)."""
-        off, sz = self._geom(offsets, sizes)
-        n, F = off.size, int(frames_per_stream)
-        out, counts, stride = self._stretch_args(
-            n, out, counts, stride, lambda hz: stretch_max_samples(hz, packed_max_samples(hz, F), 1, 2))
-        if infos is None:
-            infos = np.zeros((n, F), FRAME_INFO_DT)
-        fp, k1 = _ptr(frames)
-        op, k2 = _ptr(out)
-        cp, k3 = _ptr(counts)
-        ip, k4 = _ptr(infos)
-        self._ck(self._L.mp3d_batch_decode_stretched(self._h, fp, off.ctypes.data, sz.ctypes.data, n, F, op, stride, cp,
-                                                     _pack_flags(flush, gapless), ip, _stream(stream)))
+        head, n, F, infos, keep = self._decode_head(frames, offsets, sizes, frames_per_stream, infos)
+        hz, ch = self._out
+        out, counts, stride = self._sink_out(
+            n, out, counts, stride, self._stretch, lambda: stretch_max_samples(hz, packed_max_samples(hz, F), 1, 2),
+            (ch,), np.float32)
+        self._ck(self._L.mp3d_batch_decode_stretched(*head, _ptr(out)[0], stride, _ptr(counts)[0],
+                                                     _pack_flags(flush, gapless), _ptr(infos)[0], _stream(stream)))
         return out, counts, infos
 
     def stretch_time_us(self):
@@ -861,22 +543,6 @@ class BatchDecoder:
         self._ck(self._L.mp3d_batch_set_limiter(self._h, int(bool(on)), float(ceiling_db)))
         self._limit = float(ceiling_db) if on else None
 
-    def _limit_args(self, n, out, out_counts, gain, gr, f32, stride, default_stride):
-        hz, ch = getattr(self, "_out", (0, 0))
-        if stride is None:  # (limiter off: the call fails with MP3D_E_ARG)
-            on = getattr(self, "_limit", None) is not None
-            stride = int(out.shape[1]) if out is not None else default_stride(hz) if on else 1
-        stride = int(stride)
-        if out is None:
-            out = np.zeros((n, stride, ch), np.float32 if f32 else np.int16)
-        if out_counts is None:
-            out_counts = np.zeros(n, np.int32)
-        if gain is not None and not hasattr(gain, "data_ptr"):
-            gain = np.ascontiguousarray(gain, np.float32)
-        if gr is None:
-            gr = np.ones(n, np.float32)
-        return out, out_counts, gain, gr, stride
-
     def limit(self, samples, counts, gain=None, out=None, out_counts=None, gr=None, f32=True, flush=False, stride=None,
               stream=None):
         """The limiter alone (mp3d_batch_limit): samples float32
@@ -891,19 +557,15 @@ class BatchDecoder:
         samples of every stream and restarts it.  Returns (out, out_counts,
         gr): stream s holds out_counts[s] samples per channel (-1: over the
         stride)."""
-        n, ss = int(samples.shape[0]), int(samples.shape[1])
-        if not hasattr(counts, "data_ptr"):
-            counts = np.ascontiguousarray(counts, np.int32)
-        out, out_counts, gain, gr, stride = self._limit_args(n, out, out_counts, gain, gr, f32, stride,
-                                                             lambda hz: limiter_max_samples(hz, ss))
-        sp, k1 = _ptr(samples)
-        cp, k2 = _ptr(counts)
-        gp, k3 = _ptr(gain)
-        op, k4 = _ptr(out)
-        oc, k5 = _ptr(out_counts)
-        rp, k6 = _ptr(gr)
-        self._ck(self._L.mp3d_batch_limit(self._h, sp if ss else None, ss, cp, n, gp, op, int(bool(f32)), stride, oc, rp,
-                                          _pack_flags(flush), _stream(stream)))
+        head, n, ss, keep = self._stage_head(samples, counts)
+        hz, ch = self._out
+        out, out_counts, stride = self._sink_out(n, out, out_counts, stride, self._limit is not None,
+                                                 lambda: limiter_max_samples(hz, ss), (ch,),
+                                                 np.float32 if f32 else np.int16)
+        gain = _host(gain, np.float32)
+        gr = np.ones(n, np.float32) if gr is None else gr
+        self._ck(self._L.mp3d_batch_limit(self._h, *head, _ptr(gain)[0], _ptr(out)[0], int(bool(f32)), stride,
+                                          _ptr(out_counts)[0], _ptr(gr)[0], _pack_flags(flush), _stream(stream)))
         return out, out_counts, gr
 
     def decode_limited(self, frames, offsets, sizes, frames_per_stream, gain=None, out=None, counts=None, gr=None,
@@ -913,21 +575,16 @@ class BatchDecoder:
         stride defaults to out's, else to the bound that cannot overflow.
         flush and gapless as in decode_packed; the flush also ends the
         limiter.  Returns (out, counts, gr, infos)."""
-        off, sz = self._geom(offsets, sizes)
-        n, F = off.size, int(frames_per_stream)
-        out, counts, gain, gr, stride = self._limit_args(
-            n, out, counts, gain, gr, f32, stride, lambda hz: limiter_max_samples(hz, packed_max_samples(hz, F)))
-        if infos is None:
-            infos = np.zeros((n, F), FRAME_INFO_DT)
-        fp, k1 = _ptr(frames)
-        gp, k2 = _ptr(gain)
-        op, k3 = _ptr(out)
-        cp, k4 = _ptr(counts)
-        rp, k5 = _ptr(gr)
-        ip, k6 = _ptr(infos)
-        self._ck(self._L.mp3d_batch_decode_limited(self._h, fp, off.ctypes.data, sz.ctypes.data, n, F, gp, op,
-                                                   int(bool(f32)), stride, cp, rp,
-                                                   _pack_flags(flush, gapless), ip, _stream(stream)))
+        head, n, F, infos, keep = self._decode_head(frames, offsets, sizes, frames_per_stream, infos)
+        hz, ch = self._out
+        out, counts, stride = self._sink_out(
+            n, out, counts, stride, self._limit is not None, lambda: limiter_max_samples(hz, packed_max_samples(hz, F)),
+            (ch,), np.float32 if f32 else np.int16)
+        gain = _host(gain, np.float32)
+        gr = np.ones(n, np.float32) if gr is None else gr
+        self._ck(self._L.mp3d_batch_decode_limited(*head, _ptr(gain)[0], _ptr(out)[0], int(bool(f32)), stride,
+                                                   _ptr(counts)[0], _ptr(gr)[0], _pack_flags(flush, gapless),
+                                                   _ptr(infos)[0], _stream(stream)))
         return out, counts, gr, infos
 
     def limiter_time_us(self):
@@ -947,17 +604,6 @@ class BatchDecoder:
                                            float(preamp_db)))
         self._eq = int(arr.size)
 
-    def _eq_args(self, n, out, out_counts, stride, default_stride):
-        hz, ch = getattr(self, "_out", (0, 0))
-        if stride is None:  # (equaliser off: the call fails with MP3D_E_ARG)
-            stride = int(out.shape[1]) if out is not None else default_stride(hz) if getattr(self, "_eq", 0) else 1
-        stride = int(stride)
-        if out is None:
-            out = np.zeros((n, stride, ch), np.float32)
-        if out_counts is None:
-            out_counts = np.zeros(n, np.int32)
-        return out, out_counts, stride
-
     def eq(self, samples, counts, out=None, out_counts=None, flush=False, stride=None, stream=None):
         """The equaliser alone (mp3d_batch_eq): samples float32
         [n, sample_stride, channels] in the packed format, counts int32 [n]
@@ -969,15 +615,10 @@ class BatchDecoder:
         flush=True restarts the streams after the call.  Returns (out,
         out_counts): stream s holds out_counts[s] samples per channel (-1:
         over the stride)."""
-        n, ss = int(samples.shape[0]), int(samples.shape[1])
-        if not hasattr(counts, "data_ptr"):
-            counts = np.ascontiguousarray(counts, np.int32)
-        out, out_counts, stride = self._eq_args(n, out, out_counts, stride, lambda hz: ss)
-        sp, k1 = _ptr(samples)
-        cp, k2 = _ptr(counts)
-        op, k3 = _ptr(out)
-        oc, k4 = _ptr(out_counts)
-        self._ck(self._L.mp3d_batch_eq(self._h, sp if ss else None, ss, cp, n, op, stride, oc, _pack_flags(flush),
+        head, n, ss, keep = self._stage_head(samples, counts)
+        out, out_counts, stride = self._sink_out(n, out, out_counts, stride, self._eq, lambda: ss, (self._out[1],),
+                                                 np.float32)
+        self._ck(self._L.mp3d_batch_eq(self._h, *head, _ptr(out)[0], stride, _ptr(out_counts)[0], _pack_flags(flush),
                                        _stream(stream)))
         return out, out_counts
 
@@ -988,17 +629,12 @@ class BatchDecoder:
         defaults to out's, else to the bound that cannot overflow.  flush and
         gapless as in decode_packed; the flush also restarts the equaliser.
         Returns (out, counts, infos)."""
-        off, sz = self._geom(offsets, sizes)
-        n, F = off.size, int(frames_per_stream)
-        out, counts, stride = self._eq_args(n, out, counts, stride, lambda hz: packed_max_samples(hz, F))
-        if infos is None:
-            infos = np.zeros((n, F), FRAME_INFO_DT)
-        fp, k1 = _ptr(frames)
-        op, k2 = _ptr(out)
-        cp, k3 = _ptr(counts)
-        ip, k4 = _ptr(infos)
-        self._ck(self._L.mp3d_batch_decode_equalized(self._h, fp, off.ctypes.data, sz.ctypes.data, n, F, op, stride, cp,
-                                                     _pack_flags(flush, gapless), ip, _stream(stream)))
+        head, n, F, infos, keep = self._decode_head(frames, offsets, sizes, frames_per_stream, infos)
+        hz, ch = self._out
+        out, counts, stride = self._sink_out(n, out, counts, stride, self._eq, lambda: packed_max_samples(hz, F), (ch,),
+                                             np.float32)
+        self._ck(self._L.mp3d_batch_decode_equalized(*head, _ptr(out)[0], stride, _ptr(counts)[0],
+                                                     _pack_flags(flush, gapless), _ptr(infos)[0], _stream(stream)))
         return out, counts, infos
 
     def eq_time_us(self):
@@ -1030,21 +666,9 @@ class BatchDecoder:
         if (db is None) == (energy is None):
             raise ValueError("one of db and energy")
         if energy is None:
-            energy = [segment_threshold(getattr(self, "_out", (0, 0))[0], db)] * int(n)
+            energy = [segment_threshold(self._out[0], db)] * int(n)
         thr = np.ascontiguousarray(energy, np.uint64).reshape(-1)
         self._ck(self._L.mp3d_batch_set_segment_threshold(self._h, int(first), thr.size, thr.ctypes.data))
-
-    def _segment_args(self, n, seg, seg_counts, stride, default_stride):
-        hz, ch = getattr(self, "_out", (0, 0))
-        if stride is None:  # (sink off: the call fails with MP3D_E_ARG)
-            on = getattr(self, "_segments", None)
-            stride = int(seg.shape[1]) if seg is not None else default_stride(hz, *on) if on else 1
-        stride = int(stride)
-        if seg is None:
-            seg = np.zeros((n, stride, 2), np.int64)
-        if seg_counts is None:
-            seg_counts = np.zeros(n, np.int32)
-        return seg, seg_counts, stride
 
     def segments(self, samples, counts, seg=None, seg_counts=None, flush=False, stride=None, stream=None):
         """The segment sink alone (mp3d_batch_segments): samples float32
@@ -1057,17 +681,11 @@ class BatchDecoder:
         closed at its end, and restarts it.  Returns (seg, seg_counts): stream
         s holds seg_counts[s] pairs (start, end) in samples since its restart
         (-1: over the stride)."""
-        n, ss = int(samples.shape[0]), int(samples.shape[1])
-        if not hasattr(counts, "data_ptr"):
-            counts = np.ascontiguousarray(counts, np.int32)
-        seg, seg_counts, stride = self._segment_args(n, seg, seg_counts, stride,
-                                                     lambda hz, p, sp: segment_max(hz, ss, p, sp))
-        sp, k1 = _ptr(samples)
-        cp, k2 = _ptr(counts)
-        gp, k3 = _ptr(seg)
-        gc, k4 = _ptr(seg_counts)
-        self._ck(self._L.mp3d_batch_segments(self._h, sp if ss else None, ss, cp, n, gp, stride, gc, _pack_flags(flush),
-                                             _stream(stream)))
+        head, n, ss, keep = self._stage_head(samples, counts)
+        seg, seg_counts, stride = self._sink_out(n, seg, seg_counts, stride, self._segments is not None,
+                                                 lambda: segment_max(self._out[0], ss, *self._segments), (2,), np.int64)
+        self._ck(self._L.mp3d_batch_segments(self._h, *head, _ptr(seg)[0], stride, _ptr(seg_counts)[0],
+                                             _pack_flags(flush), _stream(stream)))
         return seg, seg_counts
 
     def decode_segments(self, frames, offsets, sizes, frames_per_stream, seg=None, counts=None, infos=None,
@@ -1077,18 +695,13 @@ class BatchDecoder:
         to the bound that cannot overflow.  flush and gapless as in
         decode_packed; the flush also ends the segments.  Returns (seg, counts,
         infos)."""
-        off, sz = self._geom(offsets, sizes)
-        n, F = off.size, int(frames_per_stream)
-        seg, counts, stride = self._segment_args(
-            n, seg, counts, stride, lambda hz, p, sp: segment_max(hz, packed_max_samples(hz, F), p, sp))
-        if infos is None:
-            infos = np.zeros((n, F), FRAME_INFO_DT)
-        fp, k1 = _ptr(frames)
-        gp, k2 = _ptr(seg)
-        cp, k3 = _ptr(counts)
-        ip, k4 = _ptr(infos)
-        self._ck(self._L.mp3d_batch_decode_segments(self._h, fp, off.ctypes.data, sz.ctypes.data, n, F, gp, stride, cp,
-                                                    _pack_flags(flush, gapless), ip, _stream(stream)))
+        head, n, F, infos, keep = self._decode_head(frames, offsets, sizes, frames_per_stream, infos)
+        hz = self._out[0]
+        seg, counts, stride = self._sink_out(
+            n, seg, counts, stride, self._segments is not None,
+            lambda: segment_max(hz, packed_max_samples(hz, F), *self._segments), (2,), np.int64)
+        self._ck(self._L.mp3d_batch_decode_segments(*head, _ptr(seg)[0], stride, _ptr(counts)[0],
+                                                    _pack_flags(flush, gapless), _ptr(infos)[0], _stream(stream)))
         return seg, counts, infos
 
     def segment_time_us(self):
@@ -1104,8 +717,8 @@ class BatchDecoder:
         in_hz)."""
         import torch
 
-        hz, ch = getattr(self, "_out", (0, 0))
-        if getattr(self, "_segments", None) is None:
+        hz, ch = self._out
+        if self._segments is None:
             raise MP3DError("long_segments needs set_segments")
         host = data.cpu().numpy().tobytes() if hasattr(data, "cpu") else bytes(data)
         cap = max(1, long_packed_bound(host, hz))
@@ -1130,10 +743,10 @@ class BatchDecoder:
         Returns (out, counts, lufs, tpeak, gain, infos): out as given, the rest
         host arrays."""
         import torch
-        if not (getattr(self, "_loud", False) and getattr(self, "_tp", False)):
+        if not (self._loud and self._tp):
             raise MP3DError("decode_normalized needs set_loudness and set_true_peak")
         if limit:
-            if getattr(self, "_limit", None) is None:
+            if self._limit is None:
                 raise MP3DError("decode_normalized(limit=True) needs set_limiter")
             if float(max_dbtp) != self._limit:
                 raise MP3DError("max_dbtp %r is not the limiter's ceiling %r" % (max_dbtp, self._limit))
@@ -1274,13 +887,10 @@ class BatchDecoder:
         return out[: n.value], si, hz.value
 
     def huffman_only(self, frames, offsets, sizes, frames_per_stream):
-        off, sz = self._geom(offsets, sizes)
-        n, F = off.size, int(frames_per_stream)
+        head, n, F, _, keep = self._decode_head(frames, offsets, sizes, frames_per_stream)
         is_out = np.zeros((n, F, 2, 2, 576), np.int16)
         sf_out = np.zeros((n, F, 2, 2, 40), np.uint8)
-        fp, k1 = _ptr(frames)
-        self._ck(self._L.mp3d_batch_huffman_only(self._h, fp, off.ctypes.data, sz.ctypes.data, n, F,
-                                             is_out.ctypes.data, sf_out.ctypes.data, None))
+        self._ck(self._L.mp3d_batch_huffman_only(*head, is_out.ctypes.data, sf_out.ctypes.data, None))
         return is_out, sf_out
 
     def synth_only(self, xr, block_type, mixed, nch, hz, pcm=None, stream=None):
@@ -1378,12 +988,6 @@ def stretch_max_samples(hz, in_samples, num=1, den=2):
     """Smallest stride of stretch that can never overflow for one call
     feeding in_samples samples at tempo num / den (mp3d_stretch_max_samples)."""
     return int(_check(lib().mp3d_stretch_max_samples(int(hz), int(in_samples), int(num), int(den))))
-
-
-EQ_MAX_BANDS = 10  # MP3D_EQ_MAX_BANDS
-EQ_PEAK, EQ_LOW_SHELF, EQ_HIGH_SHELF, EQ_HIGH_PASS, EQ_LOW_PASS = range(5)  # MP3D_EQ_*
-EQ_BAND_DT = np.dtype([("type", np.int32), ("f0_hz", np.float64), ("gain_db", np.float64), ("q", np.float64)],
-                      align=True)  # mp3d_eq_band
 
 
 def _eq_bands(bands):
