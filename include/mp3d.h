@@ -1219,6 +1219,125 @@ MP3D_API int mp3d_batch_decode_equalized(mp3d_batch *b, const uint8_t *frames, c
  * (mp3d_batch_eq, mp3d_batch_decode_equalized); needs mp3d_batch_set_timing */
 MP3D_API int mp3d_batch_eq_time(mp3d_batch *b, float *us);
 
+/* ---- pitch sink (F0 contour per 10 ms hop, YIN) ----------------------------- *
+ * The fundamental frequency of the voice, a record per 10 ms: what a player
+ * draws as a sentence's intonation contour and what a speech pipeline takes
+ * next to the log-mel frames.  The method is YIN (de Cheveigne and Kawahara,
+ * JASA 111 (4), 2002): difference function, cumulative-mean normalisation,
+ * absolute threshold, parabolic refinement; no smoothing across frames.
+ *
+ * Input signal of a slot: packed-sink output in the handle's format (any of
+ * the nine rates fs, C = out_channels 1 or 2, float32 interleaved):
+ * x_c[0 .. N) since the slot's last pitch restart.  Sample windows and
+ * MP3D_PACK_GAPLESS act before it.  As in the segment sink:
+ *   m[i] = x_0[i] (mono), 0.5f * (x_0[i] + x_1[i]) (stereo), the tempo sink's mix
+ *   q[i] = (int) clamp(floor(m[i] * 32768 + 0.5), -32768, 32767), the packed
+ *          sink's int16 rule; q outside [0, N) is 0
+ *
+ * Constants: H = (fs + 50) / 100 in integer division, W = 2 H.  Per handle:
+ * integers fmin_hz and fmax_hz with 50 <= fmin_hz < fmax_hz <= 2000 and
+ * 4 fmax_hz <= fs, and the threshold theta in units of 1/1024, 1 <= theta <=
+ * 1024.  tmin = ceil(fs / fmax_hz), tmax = floor(fs / fmin_hz), so 4 <= tmin and
+ * tmax <= 960; T = tmax + 1; SPAN = W + T, at most 1921.  Limits so close that
+ * no whole lag lies between them (11 025 Hz, 1999 and 2000: tmin 6, tmax 5) are
+ * accepted and leave every frame unvoiced.
+ *
+ * Frame f (f = 0, 1, ...) reads x_f[i] = q[f H + i], 0 <= i < SPAN.
+ *  1. Block floating point: mx = max |x_f[i]|, sh = max(0, bitlen(mx) - 10) with
+ *     bitlen(0) = 0, r[i] = x_f[i] >> sh (arithmetic).  Then |r| <= 1024, every
+ *     cross sum over W <= 960 samples stays under 2^30 and every D under 2^32.
+ *  2. For tau = 1 .. T: D(tau) = sum_{j < W} (r[j] - r[j + tau])^2, which is
+ *     Q[W] + (Q[tau + W] - Q[tau]) - 2 X(tau) with Q the prefix sum of r^2 and
+ *     X(tau) = sum_{j < W} r[j] r[j + tau]; S(tau) = sum_{k <= tau} D(k).
+ *  3. t0 is the smallest tau in [tmin, tmax] with D(tau) * tau * 1024 <
+ *     theta * S(tau): the cumulative-mean-normalised difference under
+ *     theta / 1024; both sides stay under 2^53.  Without such a tau the frame
+ *     is unvoiced and its record is {0.0f, 0.0f, 0, sh}.
+ *  4. t starts at t0; while t < tmax and D(t + 1) < D(t), t advances: the walk
+ *     to the local minimum of D (not of the normalised function, whose
+ *     comparison would need 128-bit products).
+ *  5. In double, with a = D(t - 1), b = D(t), c = D(t + 1) and den = a - 2 b + c
+ *     formed in int64: delta = den > 0 ? 0.5 * (double)(a - c) / (double)den : 0,
+ *     clamped to [-1, 1]; f0_hz = (float)(fs / (t + delta)); periodicity =
+ *     (float)max(0, 1 - (double)(b * t) / (double)S(t)).  Every operand is an
+ *     exactly represented integer, every operation one IEEE double operation,
+ *     none a contracted multiply-add.
+ *
+ * Emit rule: after N samples floor((N - SPAN) / H) + 1 frames are known (0 if
+ * N < SPAN); a call emits those that became known.  MP3D_PACK_FLUSH emits every
+ * frame with f H < N, ceil(N / H) in all, with zeros behind N; then the slot
+ * restarts.  A call that feeds in_samples emits at most mp3d_pitch_max_frames
+ * = (in_samples + SPAN + H - 2) / H frames, flushed or not and whatever was
+ * pending (the bound is reached).  Any split of a stream into calls gives the
+ * same records, bit for bit.
+ *
+ * Overflow: a slot whose call would emit more than pitch_stride frames gets
+ * count -1, writes nothing and restarts.
+ *
+ * The per-slot pitch state (N and the last min(N, SPAN - 1) <= 1920 values of
+ * q as int16) lives in the handle while the sink is set, not in the state
+ * blob.  All zero is a restarted stream.  It restarts where the segment
+ * sink's does: at create, at mp3d_batch_reset, at mp3d_batch_set_state on its
+ * slot, at mp3d_batch_set_output (which also turns the sink off), at
+ * mp3d_batch_set_pitch, at mp3d_batch_set_window on its slot, after its own
+ * flush and after an overflow.                                               */
+typedef struct {
+    float f0_hz;       /* fs / (lag + delta); 0 in an unvoiced frame            */
+    float periodicity; /* 1 - the normalised difference at lag, in [0, 1]       */
+    int32_t lag;       /* t in samples; 0 in an unvoiced frame                  */
+    int32_t shift;     /* sh of the frame's block floating point                */
+} mp3d_pitch_frame;
+
+/* host only: SPAN at rate hz for the limits, and tmin and tmax through the
+ * pointers (either may be null).  MP3D_E_ARG for a rate that is not an MPEG
+ * audio rate or for limits outside the rules above. */
+MP3D_API long long mp3d_pitch_span(int hz, int fmin_hz, int fmax_hz, int *tau_min, int *tau_max);
+
+/* host only: a pitch_stride no slot can exceed in one call that feeds
+ * in_samples (0 .. 2^31 - 1) samples: (in_samples + SPAN + H - 2) / H.
+ * MP3D_E_ARG for a bad rate or count, or an fmin_hz that no fmax_hz fits. */
+MP3D_API long long mp3d_pitch_max_frames(int hz, long long in_samples, int fmin_hz);
+
+/* Needs a packed format (mp3d_batch_set_output) and limits inside the rules
+ * above, else MP3D_E_ARG.  on != 0 sets the parameters, restarts every slot's
+ * pitch state and waits for the handle's work; on = 0 turns the sink off and
+ * frees its buffers. */
+MP3D_API int mp3d_batch_set_pitch(mp3d_batch *b, int on, int fmin_hz, int fmax_hz, int theta);
+
+/* The stage: feeds counts[s] (clamped to [0, sample_stride]) sample frames
+ * from samples + s * sample_stride * out_channels per stream through the
+ * slots' pitch state and writes the records the call emits to pitch + s *
+ * pitch_stride and their number to pitch_count[s] (-1: over pitch_stride).
+ * Nothing past pitch_count[s] records is written.  samples, counts, pitch and
+ * pitch_count are host or device memory (a host samples array is read whole; a
+ * host pitch is filled by one copy per stream); the call is asynchronous when
+ * all four are device memory.  Device pointers must be element-aligned (a
+ * device pitch to 8 bytes), else MP3D_E_ARG; sample_stride is at most 2^31 - 1
+ * - 960 and pitch_stride at most 2^31 - 1, and n_streams * ceil(bound / 8) at
+ * most (2^32 - 1) / 256, the launch's size, else MP3D_E_CAPACITY.  flags:
+ * MP3D_PACK_FLUSH only.  Runs on the device out and out_count of
+ * mp3d_batch_decode_packed (float32), of mp3d_batch_stretch, mp3d_batch_limit
+ * or mp3d_batch_eq, or with n_streams = 1 on the device output of
+ * mp3d_batch_decode_long_packed: frames are independent, so one long stream is
+ * spread over the whole GPU.  Leaves decoder, resampler and every other sink's
+ * state untouched.  MP3D_E_ARG before mp3d_batch_set_pitch.                   */
+MP3D_API int mp3d_batch_pitch(mp3d_batch *b, const float *samples, long long sample_stride, const int *counts,
+                              int n_streams, mp3d_pitch_frame *pitch, long long pitch_stride, int *pitch_count,
+                              int flags, void *hip_stream);
+
+/* mp3d_batch_decode_packed (float32) into a handle-owned buffer of stride
+ * mp3d_packed_max_samples(out_hz, frames_per_stream, 0) with device counts,
+ * then the stage on them.  flags: MP3D_PACK_FLUSH | MP3D_PACK_GAPLESS, both
+ * forwarded (the flush ends the resampler, then the pitch frames).          */
+MP3D_API int mp3d_batch_decode_pitch(mp3d_batch *b, const uint8_t *frames, const uint64_t *offsets,
+                                     const uint32_t *sizes, int n_streams, int frames_per_stream,
+                                     mp3d_pitch_frame *pitch, long long pitch_stride, int *pitch_count, int flags,
+                                     mp3d_frame_info *infos, void *hip_stream);
+
+/* device-side microseconds of the pitch stage of the last pitch call
+ * (mp3d_batch_pitch, mp3d_batch_decode_pitch); needs mp3d_batch_set_timing */
+MP3D_API int mp3d_batch_pitch_time(mp3d_batch *b, float *us);
+
 /* ---- diagnostics -------------------------------------------------------- */
 MP3D_API const char *mp3d_strerror(int err);
 MP3D_API int mp3d_last_hip_error(void);

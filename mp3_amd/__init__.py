@@ -21,7 +21,8 @@ import numpy as np
 
 from ._abi import (ABI, EQ_BAND_DT, EQ_HIGH_PASS, EQ_HIGH_SHELF, EQ_LOW_PASS, EQ_LOW_SHELF,  # noqa: F401
                    EQ_MAX_BANDS, EQ_PEAK, EXPORTS, FEAT_LOG10, FRAME_F32, FRAME_INFO_DT, FRAME_LAST, LIB_PATH,
-                   LONG_GAPLESS, MP3D_FEAT_LOG10, OPT_CRC_CHECK, PACK_FLUSH, PACK_GAPLESS, RATES, WINDOW_NO_END,
+                   LONG_GAPLESS, MP3D_FEAT_LOG10, OPT_CRC_CHECK, PACK_FLUSH, PACK_GAPLESS, PITCH_FRAME_DT, RATES,
+                   WINDOW_NO_END,
                    FrameInfo, MP3DError, StreamInfo, _bind, _check, _load, _loaded, _pack_flags, _ptr, _stream, lib,
                    library)
 
@@ -129,7 +130,8 @@ class BatchDecoder:
     _limit = None  # limiter: its ceiling in dBTP while it is on
     _segments = None  # segment sink: its pause and shortest segment in hops while it is on
     _eq = 0  # equaliser: its number of bands
-    _AFTER_PACKED = ("_mels", "_loud", "_tp", "_stretch", "_limit", "_segments", "_eq")
+    _pitch = None  # pitch sink: its lowest frequency in Hz while it is on
+    _AFTER_PACKED = ("_mels", "_loud", "_tp", "_stretch", "_limit", "_segments", "_eq", "_pitch")
 
     def __init__(self, max_streams, max_frames, device=0):
         L = self._L = lib()  # the build that owns the handle: every later call goes to it
@@ -728,6 +730,76 @@ class BatchDecoder:
         seg, cnt = self.segments(out[None, : max(n, 1)], [n], flush=True)
         return seg[0, : int(cnt[0])].copy(), pcm, si, in_hz
 
+    def set_pitch(self, on=True, fmin=60, fmax=500, threshold=0.15):
+        """Turn the pitch sink on or off (mp3d_batch_set_pitch): one record
+        (f0_hz, periodicity, lag, shift) per 10 ms of the packed output,
+        whatever its format, by YIN over the lags of fmax .. fmin Hz (integers,
+        50 <= fmin < fmax <= 2000, 4 fmax <= hz); a frame is voiced when its
+        normalised difference falls under threshold, passed on as
+        round(1024 * threshold) in 1 .. 1024.  Needs set_output.  Restarts
+        every stream's pitch state."""
+        theta = int(round(1024 * float(threshold)))
+        self._ck(self._L.mp3d_batch_set_pitch(self._h, int(bool(on)), int(fmin), int(fmax), theta))
+        self._pitch = int(fmin) if on else None
+
+    def pitch(self, samples, counts, out=None, out_counts=None, flush=False, stride=None, stream=None):
+        """The pitch sink alone (mp3d_batch_pitch): samples float32
+        [n, sample_stride, channels] in the packed format, counts int32 [n]
+        sample frames per stream (both host arrays or device tensors), e.g.
+        the device out and counts of decode_packed, stretch, limit or eq.  out:
+        None (allocate host) or a PITCH_FRAME_DT array [n, stride] (a device
+        tensor: 16 bytes per record, e.g. int32 [n, stride, 4]); out_counts
+        int32 [n].  stride defaults to out's, else to pitch_max_frames.
+        flush=True emits every frame that starts inside the stream, zeros
+        behind its end, and restarts it.  Returns (out, out_counts): stream s
+        holds out_counts[s] records (-1: over the stride)."""
+        head, n, ss, keep = self._stage_head(samples, counts)
+        out, out_counts, stride = self._sink_out(n, out, out_counts, stride, self._pitch is not None,
+                                                 lambda: pitch_max_frames(self._out[0], ss, self._pitch), (),
+                                                 PITCH_FRAME_DT)
+        self._ck(self._L.mp3d_batch_pitch(self._h, *head, _ptr(out)[0], stride, _ptr(out_counts)[0],
+                                          _pack_flags(flush), _stream(stream)))
+        return out, out_counts
+
+    def decode_pitch(self, frames, offsets, sizes, frames_per_stream, out=None, counts=None, infos=None,
+                     flush=False, stride=None, stream=None, gapless=False):
+        """Decode as decode_packed does (float32) and write every stream's
+        pitch records (mp3d_batch_decode_pitch).  stride defaults to out's,
+        else to the bound that cannot overflow.  flush and gapless as in
+        decode_packed; the flush also ends the pitch frames.  Returns (out,
+        counts, infos)."""
+        head, n, F, infos, keep = self._decode_head(frames, offsets, sizes, frames_per_stream, infos)
+        hz = self._out[0]
+        out, counts, stride = self._sink_out(
+            n, out, counts, stride, self._pitch is not None,
+            lambda: pitch_max_frames(hz, packed_max_samples(hz, F), self._pitch), (), PITCH_FRAME_DT)
+        self._ck(self._L.mp3d_batch_decode_pitch(*head, _ptr(out)[0], stride, _ptr(counts)[0],
+                                                 _pack_flags(flush, gapless), _ptr(infos)[0], _stream(stream)))
+        return out, counts, infos
+
+    def pitch_time_us(self):
+        """Device-side microseconds of the pitch stage of the last pitch call
+        (after set_timing)."""
+        return self._stage_us(self._L.mp3d_batch_pitch_time)
+
+    def long_pitch(self, data, segment_frames=32, gapless=True):
+        """The F0 contour of one file: decode_long_packed at the handle's
+        format into a tensor on the handle's device, then pitch(flush=True) on
+        it as one stream.  Needs set_pitch.  Returns (PITCH_FRAME_DT [k], the
+        pcm tensor [n, channels], StreamInfo, in_hz)."""
+        import torch
+
+        hz, ch = self._out
+        if self._pitch is None:
+            raise MP3DError("long_pitch needs set_pitch")
+        host = data.cpu().numpy().tobytes() if hasattr(data, "cpu") else bytes(data)
+        cap = max(1, long_packed_bound(host, hz))
+        out = torch.zeros((cap, ch), dtype=torch.float32, device="cuda:%d" % self.device)
+        pcm, si, in_hz = self.decode_long_packed(data, hz, ch, segment_frames, out=out, gapless=gapless)
+        n = int(pcm.shape[0])
+        rec, cnt = self.pitch(out[None, : max(n, 1)], [n], flush=True)
+        return rec[0, : int(cnt[0])].copy(), pcm, si, in_hz
+
     def decode_normalized(self, frames, offsets, sizes, frames_per_stream, target=-23.0, max_dbtp=-1.0, out=None,
                           f32=True, gapless=False, limit=False):
         """Decode streams that are whole in this call and normalise them to
@@ -1045,6 +1117,21 @@ def max_frame_slots(nbytes):
     """Upper bound on the frame slots in nbytes of stream: the smallest
     Layer III frame is 24 B (MPEG-2 LSF, 8 kbps at 24 kHz; MPEG-1: 96 B)."""
     return int(nbytes) // 24 + 2
+
+
+def pitch_span(hz, fmin, fmax):
+    """(SPAN, tmin, tmax) of the pitch sink at rate hz for the limits fmin and
+    fmax in Hz: the samples a frame reads and its lag range
+    (mp3d_pitch_span; no GPU needed)."""
+    lo, hi = ctypes.c_int(), ctypes.c_int()
+    span = _check(lib().mp3d_pitch_span(int(hz), int(fmin), int(fmax), ctypes.byref(lo), ctypes.byref(hi)))
+    return int(span), lo.value, hi.value
+
+
+def pitch_max_frames(hz, in_samples, fmin):
+    """Smallest stride of pitch records that can never overflow for one call
+    feeding in_samples samples (mp3d_pitch_max_frames)."""
+    return int(_check(lib().mp3d_pitch_max_frames(int(hz), int(in_samples), int(fmin))))
 
 
 def long_plan(data, segment_frames=32, max_frames=None):

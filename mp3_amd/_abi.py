@@ -43,6 +43,8 @@ EQ_MAX_BANDS = 10  # MP3D_EQ_MAX_BANDS
 EQ_PEAK, EQ_LOW_SHELF, EQ_HIGH_SHELF, EQ_HIGH_PASS, EQ_LOW_PASS = range(5)  # MP3D_EQ_*
 EQ_BAND_DT = np.dtype([("type", np.int32), ("f0_hz", np.float64), ("gain_db", np.float64), ("q", np.float64)],
                       align=True)  # mp3d_eq_band
+PITCH_FRAME_DT = np.dtype([("f0_hz", np.float32), ("periodicity", np.float32), ("lag", np.int32),
+                           ("shift", np.int32)])  # mp3d_pitch_frame
 
 
 def _abi():
@@ -144,6 +146,12 @@ def _abi():
         "mp3d_batch_eq": (i, one + [vp, ll, vp, i, vp]),
         "mp3d_batch_decode_equalized": (i, dec + [vp, ll, vp] + tail),
         "mp3d_batch_eq_time": time,
+        "mp3d_pitch_span": (ll, [i, i, i, ip, ip]),
+        "mp3d_pitch_max_frames": (ll, [i, ll, i]),
+        "mp3d_batch_set_pitch": (i, [vp, i, i, i, i]),
+        "mp3d_batch_pitch": (i, one + [vp, ll, vp, i, vp]),
+        "mp3d_batch_decode_pitch": (i, dec + [vp, ll, vp] + tail),
+        "mp3d_batch_pitch_time": time,
     }
 
 

@@ -31,13 +31,15 @@ def _stale(target, deps):
 FILE_FLAGS = {"mp3d_synth.hip": ["-fno-slp-vectorize"]}
 HIP_SRCS = ["mp3d_demux.hip", "mp3d_huffman.hip", "mp3d_synth.hip", "mp3d_resample.hip", "mp3d_features.hip",
             "mp3d_loudness.hip", "mp3d_normalize.hip", "mp3d_stretch.hip", "mp3d_limiter.hip", "mp3d_segment.hip",
-            "mp3d_eq.hip",
+            "mp3d_eq.hip", "mp3d_pitch.hip",
             "mp3d_host_tables.cpp", "mp3d_batch.cpp", "mp3d_long.cpp",
             "mp3d_dec.cpp", "mp3d_sinks.cpp", "mp3d_loudness.cpp", "mp3d_normalize.cpp",
-            "mp3d_stretch.cpp", "mp3d_limiter.cpp", "mp3d_segment.cpp", "mp3d_eq.cpp"]
+            "mp3d_stretch.cpp", "mp3d_limiter.cpp", "mp3d_segment.cpp", "mp3d_eq.cpp",
+            "mp3d_pitch.cpp"]
 HIP_HDRS = ["mp3d_internal.h", "mp3d_tables.h", "mp3d_consts.h", "mp3d_device.h", "mp3d_hostparse.h",
             "mp3d_demux_dev.h", "mp3d_huffman_dev.h", "mp3d_resample.h", "mp3d_features.h", "mp3d_loudness.h",
             "mp3d_normalize.h", "mp3d_tp_chain.h", "mp3d_stretch.h", "mp3d_limiter.h", "mp3d_segment.h", "mp3d_eq.h",
+            "mp3d_pitch.h",
             "mp3d_launch.h", "mp3d_host.h"]
 
 

@@ -2,7 +2,7 @@
  * mp3d_host.h -- private to the host sources (mp3d_host_tables.cpp,
  * mp3d_batch.cpp, mp3d_long.cpp, mp3d_dec.cpp, mp3d_sinks.cpp,
  * mp3d_loudness.cpp, mp3d_normalize.cpp, mp3d_stretch.cpp, mp3d_limiter.cpp,
- * mp3d_segment.cpp, mp3d_eq.cpp):
+ * mp3d_segment.cpp, mp3d_eq.cpp, mp3d_pitch.cpp):
  * the error macros, the readers of the environment's knobs, the owning types
  * (DevBuf device memory, PinBuf pinned host memory, Event), the batch handle,
  * the frame that every call shares -- the core decode (DecodeCall,
@@ -37,6 +37,7 @@
 #include "mp3d_limiter.h"
 #include "mp3d_segment.h"
 #include "mp3d_eq.h"
+#include "mp3d_pitch.h"
 #include "mp3d_launch.h"
 
 namespace mp3d {
@@ -421,6 +422,18 @@ struct mp3d_batch {
             K = 0;
         }
     } eq;
+    /* pitch sink (mp3d_batch_set_pitch; mp3d_pitch.h): on = false is off, and
+     * then none of its buffers exists.  st and plan hold max_streams entries. */
+    struct PitchSink : Stage {
+        bool on = false;
+        int H = 0, T = 0, tmin = 0, theta = 0; /* the hop, tmax + 1 and tmin in samples; the threshold in 1/1024 */
+        mp3d::DevBuf<PtState> st;
+        mp3d::DevBuf<PtPlan> plan;
+        void off() {
+            Stage::off(), st.release(), plan.release();
+            on = false, H = T = tmin = theta = 0;
+        }
+    } pt;
 };
 
 namespace mp3d {
@@ -481,7 +494,7 @@ inline bool is_device_ptr(const void *p, int device) { return ptr_kind(p, device
  * stage's timer owns its events). */
 /* they read the packed sink's format: off with any change of it */
 inline void stages_off(mp3d_batch *b) {
-    b->ft.off(), b->ld.off(), b->nm.off(), b->ga.off(), b->sx.off(), b->lm.off(), b->sg.off(), b->eq.off();
+    b->ft.off(), b->ld.off(), b->nm.off(), b->ga.off(), b->sx.off(), b->lm.off(), b->sg.off(), b->eq.off(), b->pt.off();
 }
 template <class S> hipError_t stage_restart(const DevBuf<S> &st, int first, int n, hipStream_t s) {
     return st ? hipMemsetAsync(st + first, 0, sizeof(S) * (size_t)n, s) : hipSuccess;
@@ -495,6 +508,7 @@ inline int stages_restart(mp3d_batch *b, int first, int n, hipStream_t s) {
     HIPCHK(stage_restart(b->lm.st, first, n, s));
     HIPCHK(stage_restart(b->sg.st, first, n, s));
     HIPCHK(stage_restart(b->eq.st, first, n, s));
+    HIPCHK(stage_restart(b->pt.st, first, n, s));
     return MP3D_OK;
 }
 

@@ -11,7 +11,7 @@
 #include <stdint.h>
 
 /* (layouts: mp3d_internal.h, mp3d_resample.h, mp3d_features.h, mp3d_loudness.h, mp3d_normalize.h,
- * mp3d_stretch.h, mp3d_limiter.h, mp3d_segment.h, mp3d_eq.h) */
+ * mp3d_stretch.h, mp3d_limiter.h, mp3d_segment.h, mp3d_eq.h, mp3d_pitch.h) */
 struct StreamState; struct FrameRec; struct UnitMeta; struct DevTables;
 struct RsState; struct RsCfg; struct RsPlan; struct RsLong;
 struct FtState; struct FtPlan; struct FtTab;
@@ -21,6 +21,7 @@ struct StState; struct StPlan;
 struct LimState; struct LimPlan;
 struct SgState; struct SgPlan;
 struct EqState; struct EqPlan; struct EqTab;
+struct PtState; struct PtPlan;
 
 namespace mp3d {
 
@@ -141,6 +142,13 @@ void launch_segments(const float *samples, const int32_t *counts, SgState *st, S
 void launch_eq(const float *samples, const int32_t *counts, EqState *st, EqPlan *plan, const EqTab *tab,
                const double *tpow, double *tz, double *entry, float *out, int32_t *out_count, int K, int ch, int n,
                long long sample_stride, long long out_stride, int tiles, int flush, hipStream_t strm);
+
+/* ---- mp3d_pitch.hip ---- */
+/* k_pt_plan + k_pt_frames + k_pt_update: packed float32 samples to one 16-byte record (f0, periodicity, lag,
+ * shift) per 10 ms frame; rec holds n * pitch_stride records; T = tmax + 1 lags over a window of 2 H samples */
+void launch_pitch(const float *samples, const int32_t *counts, PtState *st, PtPlan *plan, void *rec,
+                  int32_t *rec_count, int ch, int n, long long sample_stride, long long pitch_stride, int tiles, int fs,
+                  int H, int T, int tmin, int theta, int flush, hipStream_t strm);
 
 } // namespace mp3d
 
